@@ -6,13 +6,18 @@ One "step" = one pass of the hot path over one tile of synthetic participants re
   per-clerk modular sum             ->  exact 128-bit accumulators [n][B]
 An *element* is one (participant, vector component) pair, so a step processes P_tile * dim elements.
 Default workload = BASELINE config 3 (configs[2]): packed Shamir t=1, k=3, n=8, dim 1,048,576, 62-bit
-prime, 100k participants (the configuration the north-star target is quoted on).  The K timed steps
-cover ALL of them: a step = 100000 / K participants, issued as resident sub-tiles of <= 2500
-(50 steps x 2000; 20 steps x 2 x 2500); `config.workload` is derived from what was processed and
-`config.inputs` says what was shared (default: one resident tile replayed; --inputs distinct: 100k different
-participants).  `--workload additive` = config 2 (configs[1]); at N=1 short runs of it, of config 5's dimension (with
-the reveal), of config 4's shape and of tss's PSS_155_728_100 (transform kernel) are attached to the JSON line as
-`additional_workloads`.
+prime, 100k participants (the configuration the north-star target is quoted on).  A step is a FIXED
+amount of work: one twentieth of the workload's BASELINE job (5,000 participants at config 3, issued as resident
+sub-tiles of <= 2500: 2 x 2500), so `--steps K` times K steps and `--steps 20` is exactly the whole job; --participants P
+instead spreads P participants over the K steps.  `config.workload` is derived from what was processed and
+`config.inputs` says what was shared (default: one resident tile replayed; --inputs distinct: different participants
+in every sub-tile).  `--workload additive` = config 2 (configs[1]).
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps, the outputs of the
+timed path if --dump-outputs DIR is given, the result line.  `--full` adds everything else the bench measures or checks:
+the verification (reconstruct == column sums of the secrets) with the reveal's timing, the CPU baseline, and the attached
+runs - at N=1 short runs of config 2, of config 5's dimension (with the reveal), of config 4's shape, of tss's
+PSS_155_728_100 (transform kernel) and more, at N > 1 configs 4 and 5 sharded over the ranks - as `additional_workloads`.
 
 N > 1: one process per GPU (torchrun), participants sharded across ranks, no collective on the data path,
 ONE modular reduce of the partial clerk sums over RCCL at the end of the timed region - the library's own
@@ -87,6 +92,7 @@ WORKLOADS = {
                           desc="BASELINE config 5 per-GPU share: packed Shamir t=1 k=3 n=8, dim 16777216, 62-bit prime, Lagrange reveal"),
 }
 TILE_MAX = 2500      # participants resident per launch (secrets 21 GB + two share buffers of 56 GB at config 3)
+JOB_STEPS = 20       # a step = the BASELINE job / JOB_STEPS participants: the driver's `--steps 20` runs the whole job
 
 
 def prime_of(w):
@@ -96,6 +102,12 @@ def prime_of(w):
 def roots_of(w):
     """(omega_secrets, omega_shares) of a packed workload"""
     return (w["w2"], w["w3"]) if "w2" in w else (OMEGA[w["o2"]], OMEGA[w["o3"]])
+
+
+def run_participants(w, steps, participants=0):
+    """participants per GPU over the whole run: `participants` when given, else `steps` steps of a fixed size (the workload's
+    BASELINE job / JOB_STEPS), so that the timed work grows with --steps and ms_per_step does not depend on it"""
+    return participants or steps * -(-w["participants"] // JOB_STEPS)
 
 
 def plan_steps(target_participants, steps, tile_max):
@@ -565,6 +577,46 @@ def _verify(env, scheme, secrets, total, P, dim, B, firsts, q=P62):
     return verified, reveal
 
 
+DUMP_BYTES = 60_000_000      # --dump-outputs: .npy data of one run, in all (the limit is 64 MB)
+DUMP_SHARES = 1 << 19        # elements of the last tile's shares in the sample
+
+
+def _dump_sample(count, limit, salt):
+    """a fixed, seeded choice of at most `limit` distinct flat positions in [0, count), ascending (all of them if count <= limit)"""
+    import numpy as np
+    if count <= limit:
+        return np.arange(count, dtype=np.int64)
+    return np.sort(np.random.default_rng([SEED & 0xFFFFFFFF, salt]).choice(count, size=limit, replace=False)).astype(np.int64)
+
+
+def dump_outputs(env, out_dir, sums, shares, B):
+    """--dump-outputs: what the timed path hands its caller after its last step, as DIR/<name>.npy - the clerk sums [n][B] after
+    the exchange (a seeded sample only if they exceed the byte budget) and a fixed seeded sample of the shares of the last tile
+    this rank generated ([n][P][Bs], valid columns < B).  Residues (< 2^62) do not fit a float64 mantissa, so each array is
+    written as two exact float64 halves: value = hi31 * 2^31 + lo31.  Returns what was written (for the details file)."""
+    import numpy as np
+    torch = env.torch
+    n, P, Bs = shares.shape
+    share_idx = _dump_sample(n * P * B, DUMP_SHARES, 1)
+    sum_idx = _dump_sample(n * B, DUMP_BYTES // 16 - len(share_idx), 2)
+    f = torch.from_numpy(share_idx).to(env.dev)
+    pos = f // (P * B) * (P * Bs) + f % (P * B) // B * Bs + f % B          # (clerk, participant, column) -> offset in the buffer
+    arrays = {"clerk_sums": sums.reshape(-1)[torch.from_numpy(sum_idx).to(env.dev)],
+              "last_tile_shares": shares.reshape(-1)[pos]}
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        x = t.cpu().numpy()
+        for half, v in (("hi31", x >> 31), ("lo31", x & 0x7FFFFFFF)):
+            np.save(os.path.join(out_dir, f"{name}_{half}.npy"), v.astype(np.float64))
+            files[f"{name}_{half}.npy"] = len(v)
+    return {"dir": os.path.abspath(out_dir), "files": files,
+            "clerk_sums": f"[{n}][{B}] int64 flattened" + ("" if len(sum_idx) == n * B else f", seeded sample of {len(sum_idx)}"),
+            "last_tile_shares": f"[{n}][{P}][{B}] int64 flattened" + ("" if len(share_idx) == n * P * B else
+                                                                       f", seeded sample of {len(share_idx)}"),
+            "encoding": "float64 halves: value = hi31 * 2^31 + lo31"}
+
+
 def _line(env, name, w, dim, n, k, t, P, n_sub, steps, warmup, dt, Bs, rounds, schedule, share_map=None):
     world = env.world
     participants_total = world * steps * n_sub * P
@@ -575,8 +627,9 @@ def _line(env, name, w, dim, n, k, t, P, n_sub, steps, warmup, dt, Bs, rounds, s
         "metric": "share-gen + clerk-sum elements/sec (mod q)", "value": value, "unit": "elements/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
         "higher_is_better": True, "scaling": "weak",
-        "scaling_note": "WEAK: every GPU processes the whole per-GPU workload named in config.workload (BASELINE config 3: 100,000 "
-                        "participants PER GPU unless --participants says otherwise), so `value` grows with N at fixed time; the "
+        "scaling_note": "WEAK: every GPU processes the whole per-GPU workload named in config.workload (BASELINE config 3: 5,000 "
+                        "participants PER GPU per step, 100,000 at --steps 20, unless --participants says otherwise), so `value` "
+                        "grows with N at fixed time; the "
                         "legs under additional_workloads at N > 1 (BASELINE configs 4 and 5) are STRONG-scaled instead: their "
                         "job is fixed and its participants are divided over the N ranks (each leg says so in its own `scaling`)",
         "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -660,7 +713,7 @@ INPUT_MODES = {
 }
 
 
-def measure_fused(env, name, dim, P, n_sub, steps, warmup, row_align=16, verify=True, rounds=20, inputs="replay"):
+def measure_fused(env, name, dim, P, n_sub, steps, warmup, row_align=16, verify=True, rounds=20, inputs="replay", dump=None):
     """Software-pipelined schedule: ONE dual-role launch per sub-tile generates sub-tile i while the clerk sums of
     sub-tile i-1 are accumulated (sda_share_generator_generate_combine_dev); K tiles take K + 1 launches.
     A step = n_sub sub-tiles of P participants."""
@@ -769,6 +822,7 @@ def measure_fused(env, name, dim, P, n_sub, steps, warmup, row_align=16, verify=
     exchange_ms = (time.perf_counter() - tx) * 1e3
     env.barrier()
     dt = env.max_over_ranks(time.perf_counter() - t0)
+    outputs = dump_outputs(env, dump, total, shares[(tiles - 1) % 2], B) if dump and rank == 0 else None
     wd.phase(f"verify: {name}")
     ms = C.c_float()
     launch_ms = []
@@ -818,12 +872,14 @@ def measure_fused(env, name, dim, P, n_sub, steps, warmup, row_align=16, verify=
     res["exchange_ms"] = env.max_over_ranks(exchange_ms)      # the cross-GPU modular reduce, inside the timed region
     res["exchange_bytes_per_gpu"] = 8 * n * B
     res["config"]["allocation"] = ("one arena, buffers %d bytes apart" % arena_pad) if arena_pad >= 0 else "separate allocations"
+    if outputs:
+        res["outputs"] = outputs
     del secrets, shares, sums, total, arena
     torch.cuda.empty_cache()
     return res
 
 
-def measure(env, name, dim, P, n_sub, steps, warmup, row_align=16, overlap=0, verify=True, rounds=20):
+def measure(env, name, dim, P, n_sub, steps, warmup, row_align=16, overlap=0, verify=True, rounds=20, dump=None):
     """serial schedule: share-gen launch then clerk-sum launch per sub-tile (clean per-kernel timings)"""
     torch, capi, lib, dev = env.torch, env.capi, env.lib, env.dev
     rank, world = env.rank, env.world
@@ -903,6 +959,7 @@ def measure(env, name, dim, P, n_sub, steps, warmup, row_align=16, overlap=0, ve
     exchange_ms = (time.perf_counter() - tx) * 1e3
     env.barrier()
     dt = env.max_over_ranks(time.perf_counter() - t0)
+    outputs = dump_outputs(env, dump, total, shares[(tiles - 1) % nbuf], B) if dump and rank == 0 else None
     wd.phase(f"verify: {name}")
     gen_ms = comb_ms = 0.0
     ms = C.c_float()
@@ -941,6 +998,8 @@ def measure(env, name, dim, P, n_sub, steps, warmup, row_align=16, overlap=0, ve
     res["reveal"] = reveal
     res["exchange_ms"] = env.max_over_ranks(exchange_ms)      # the cross-GPU modular reduce, inside the timed region
     res["exchange_bytes_per_gpu"] = 8 * n * B
+    if outputs:
+        res["outputs"] = outputs
     del secrets, shares, sums, total
     torch.cuda.empty_cache()
     return res
@@ -1084,13 +1143,14 @@ def self_launch(n, deadline_s=0.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=JOB_STEPS,
+                    help="timed steps; a step is a fixed share of the BASELINE job (1/%d of it) unless --participants is given" % JOB_STEPS)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="packed", choices=sorted(WORKLOADS))
     ap.add_argument("--dim", type=int, default=0, help="vector dimension (default: the workload's, 1048576 unless stated)")
     ap.add_argument("--participants", type=int, default=0,
-                    help="participants per GPU over the whole run (default: the BASELINE configuration's count); a step "
-                         "covers participants / steps of them, issued as resident sub-tiles of at most --tile")
+                    help="participants per GPU over the whole run (default: --steps x the BASELINE configuration's count / %d); "
+                         "a step covers participants / steps of them, issued as resident sub-tiles of at most --tile" % JOB_STEPS)
     ap.add_argument("--tile", type=int, default=0, help=f"largest resident sub-tile, participants (default {TILE_MAX})")
     ap.add_argument("--row-align", type=int, default=16, help="pad share rows to a multiple of this many elements")
     ap.add_argument("--overlap", type=int, default=0,
@@ -1105,6 +1165,12 @@ def main():
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "fresh"],
                     help="the ONE-thread CPU baseline is always timed on this box; the all-cores thread sweep (~100 s) is taken from "
                          "profiles/cpu_baseline_hosts.json when it knows this host type and workload (auto) or always measured (fresh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the verification (with the reveal's timing), the CPU "
+                         "baseline and the attached workloads; the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path computed (clerk sums, a seeded sample of the last "
+                         "tile's shares) as DIR/<name>.npy, float64, at most %d bytes in all" % DUMP_BYTES)
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-additional", action="store_true",
                     help="skip the attached runs (N = 1: short config-2 and config-5-shape runs; N > 1: BASELINE configs 4 and 5 "
@@ -1149,17 +1215,20 @@ def main():
     wd.phase("start")
     env = Env(wd)
 
-    def run(name, steps, warmup, participants=0, dim=0, tile=0, rounds=0, inputs=None):
+    verify = args.full and not args.no_verify
+
+    def run(name, steps, warmup, participants=0, dim=0, tile=0, rounds=0, inputs=None, dump=None):
         w = WORKLOADS[name]
         dim = dim or w.get("dim", 1 << 20)
         n_sub, p_sub = plan_steps(participants or w["participants"], steps, tile or w.get("tile_max", TILE_MAX))
         if args.schedule == "fused" and not args.overlap:
-            return measure_fused(env, name, dim, p_sub, n_sub, steps, warmup, args.row_align, verify=not args.no_verify,
-                                 rounds=rounds or args.drbg_rounds, inputs=inputs or args.inputs)
-        return measure(env, name, dim, p_sub, n_sub, steps, warmup, args.row_align, args.overlap, verify=not args.no_verify,
-                       rounds=rounds or args.drbg_rounds)
+            return measure_fused(env, name, dim, p_sub, n_sub, steps, warmup, args.row_align, verify=verify,
+                                 rounds=rounds or args.drbg_rounds, inputs=inputs or args.inputs, dump=dump)
+        return measure(env, name, dim, p_sub, n_sub, steps, warmup, args.row_align, args.overlap, verify=verify,
+                       rounds=rounds or args.drbg_rounds, dump=dump)
 
-    line = run(args.workload, args.steps, args.warmup, args.participants, args.dim, args.tile)
+    line = run(args.workload, args.steps, args.warmup, run_participants(WORKLOADS[args.workload], args.steps, args.participants),
+               args.dim, args.tile, dump=args.dump_outputs)
     line["rccl"] = env.rccl
     line["build_id"] = env.lib.sda_build_id().decode()
     line["kernel_id"] = env.lib.sda_kernel_id().decode()
@@ -1172,7 +1241,7 @@ def main():
     line["library"] = env.lib.sda_version().decode()
     keep = ("value", "unit", "n_gpus", "steps", "ms_per_step", "config", "kernels", "roofline", "path_roofline",
             "verified_reconstruct_equals_sum", "verified_against", "reveal", "exchange_ms", "exchange_bytes_per_gpu")
-    if env.world == 1 and not args.no_additional and args.workload == "packed":
+    if env.world == 1 and args.full and not args.no_additional and args.workload == "packed":
         # BASELINE config 2 (additive 3-way, 10k participants = 5 steps of 2000)
         add = run("additive", 5, 2)
         # BASELINE configs 4 and 5 at their FULL job size on this one GPU (they are defined on 8 GPUs; with one GPU they are
@@ -1232,7 +1301,7 @@ def main():
             r = run("packed26", 20, 1, participants=(args.leg_participants or 50_000), dim=args.leg_dim or 0, tile=1250, rounds=12)
             r["rounds"] = 12
             line["additional_workloads"]["config4_chacha12"] = {k: r[k] for k in keep + ("rounds",) if k in r}
-    if env.world > 1 and not args.no_additional and args.workload == "packed":
+    if env.world > 1 and args.full and not args.no_additional and args.workload == "packed":
         # The two BASELINE configurations that are DEFINED on several GPUs, sharded over the ranks that
         # are here: config 4 = 1,000,000 participants of packed Shamir t=2 k=8 n=26; config 5 = 100,000 participants at
         # dim 16,777,216 with the Lagrange reveal.  Whole job / world participants per GPU (strong scaling in N for these
@@ -1249,11 +1318,12 @@ def main():
                                   f"= {per_gpu} per GPU" + (", Lagrange reveal included (reveal.ms)" if leg == "packed_dim16m" else ""))
             legs["config4_packed26" if leg == "packed26" else "config5_packed_dim16m"] = {k: r[k] for k in keep + ("scaling",) if k in r}
         line["additional_workloads"] = legs
-    wd.phase("cpu baseline on rank 0's host cores" if env.rank == 0 and not args.no_cpu_baseline else "waiting for rank 0")
+    cpu = args.full and not args.no_cpu_baseline
+    wd.phase("cpu baseline on rank 0's host cores" if env.rank == 0 and cpu else "waiting for rank 0")
     if env.rank == 0:
         # rank 0's host cores, at any world size (the other ranks wait at the closing barrier): the reference's CPU path
         # timed beside the GPU figure on the same box
-        line["cpu_baseline"] = (None if args.no_cpu_baseline else
+        line["cpu_baseline"] = (None if not cpu else
                                 cpu_baseline(WORKLOADS[args.workload], args.dim or WORKLOADS[args.workload].get("dim", 1 << 20),
                                              name=args.workload, mode=args.cpu_baseline))
     if env.use_dist:

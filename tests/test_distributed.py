@@ -149,6 +149,27 @@ def test_bench_leg_planning_covers_the_baseline_jobs_exactly():
     assert 8 * 26 * -(-(1 << 20) // 8) == 27_262_976 and 8 * 8 * -(-(1 << 24) // 3) == 357_913_984
 
 
+def test_bench_steps_set_the_timed_work():
+    """--steps K times K steps of a FIXED size (the workload's BASELINE job / 20: --steps 20 is the whole job), so the timed work
+    and not the step size follows K; --participants P spreads P participants over the K steps instead"""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_steps", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    w = bench.WORKLOADS["packed"]
+    assert bench.run_participants(w, 20) == w["participants"] == 100_000
+    for steps in (1, 3, 20, 50, 400):
+        total = bench.run_participants(w, steps)
+        assert total == steps * 5000 and bench.plan_steps(total, steps, bench.TILE_MAX) == (2, 2500)
+    for name, w in bench.WORKLOADS.items():
+        tile = w.get("tile_max", bench.TILE_MAX)
+        plans = {bench.plan_steps(bench.run_participants(w, s), s, tile) for s in (1, 7, 20, 50)}
+        assert len(plans) == 1, (name, plans)                         # the same step whatever K is
+    assert bench.run_participants(w, 7, 700) == 700
+
+
 def test_bench_starts_its_own_ranks_and_reports_the_first_failure():
     """`python bench.py --gpus 2` with no launcher (the command form the driver uses): the script becomes the launcher of its
     two ranks.  Without a GPU every rank fails at device selection - the launcher must come back promptly with a non-zero

@@ -1145,7 +1145,7 @@ def test_bench_under_torchrun_single_rank_rccl(gpu, tmp_path):
     env = dict(os.environ, SDA_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", _free_port(), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--participants", "128", "--dim", "65536", "--no-cpu-baseline", "--no-additional"]
+           "--warmup", "1", "--participants", "128", "--dim", "65536", "--full", "--no-cpu-baseline", "--no-additional"]
     line, d, _ = _run_bench(cmd, tmp_path, env=env, timeout=600)
     assert d["n_gpus"] == 1 and d["verified_reconstruct_equals_sum"] is True and line["verified_reconstruct_equals_sum"] is True
     assert d["roofline"]["bound"] in ("hbm", "valu") and d["value"] > 0
@@ -1471,7 +1471,7 @@ def test_bench_two_ranks_rccl_refusal_falls_back_loudly(gpu, tmp_path):
     env = dict(os.environ, SDA_SHARE_GPU="try")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--participants", "120", "--dim", "65536", "--no-additional", "--no-cpu-baseline"]
+           "--participants", "120", "--dim", "65536", "--full", "--no-additional", "--no-cpu-baseline"]
     compact, line, out = _run_bench(cmd, tmp_path, env=env, timeout=600)
     assert line["n_gpus"] == 2 and line["verified_reconstruct_equals_sum"] is True
     assert compact["n_gpus"] == 2 and compact["rccl"]["unique_devices"] == 1 and "exchange_ms" in compact
@@ -1514,7 +1514,7 @@ def test_bench_multi_rank_rehearsal_on_one_gpu(gpu, ranks, extra, tmp_path):
     env = dict(os.environ, SDA_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "3",
-           "--warmup", "1", "--participants", "120", "--dim", "65536", "--no-additional", "--no-cpu-baseline"] + extra
+           "--warmup", "1", "--participants", "120", "--dim", "65536", "--full", "--no-additional", "--no-cpu-baseline"] + extra
     compact, line, _ = _run_bench(cmd, tmp_path, env=env, timeout=600)
     assert line["n_gpus"] == ranks and line["verified_reconstruct_equals_sum"] is True
     assert compact["config"]["participants_total"] == ranks * 3 * 40 and compact["scaling"] == "weak"
@@ -1536,7 +1536,7 @@ def test_bench_multi_gpu_legs_configs_4_and_5(gpu, tmp_path):
     env = dict(os.environ, SDA_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--participants", "120", "--dim", "65536", "--no-cpu-baseline", "--leg-participants", "400", "--leg-dim", "98304"]
+           "--participants", "120", "--dim", "65536", "--full", "--no-cpu-baseline", "--leg-participants", "400", "--leg-dim", "98304"]
     compact, line, _ = _run_bench(cmd, tmp_path, env=env, timeout=900)
     assert line["verified_reconstruct_equals_sum"] is True and line["scaling"] == "weak"
     legs = line["additional_workloads"]
@@ -1564,7 +1564,7 @@ def test_bench_launches_its_own_ranks(gpu, tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--participants", "120", "--dim", "65536",
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--participants", "120", "--dim", "65536", "--full",
             "--leg-participants", "400", "--leg-dim", "98304"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "SDA_SHARE_GPU")}
     compact, line, _ = _run_bench([sys.executable, os.path.join(root, "bench.py")] + args, tmp_path, env=dict(env, SDA_SHARE_GPU="1"))
@@ -1627,7 +1627,7 @@ def test_bench_single_gpu_line_carries_configs_4_and_5_as_full_jobs(gpu, tmp_pat
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--participants", "64", "--dim", "65536",
-           "--no-cpu-baseline", "--leg-participants", "300", "--leg-dim", "98304"]
+           "--full", "--no-cpu-baseline", "--leg-participants", "300", "--leg-dim", "98304"]
     compact, line, _ = _run_bench(cmd, tmp_path)
     legs = line["additional_workloads"]
     assert {"config4_full", "config5_full", "additive", "packed_pss728", "narrow_ref", "narrow26_ref", "narrow_pss728", "narrow_pss19682",
@@ -1672,11 +1672,50 @@ def test_bench_distinct_inputs_mode(gpu, tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--participants", "320", "--tile", "32",
-           "--dim", "65536", "--no-cpu-baseline", "--no-additional", "--inputs", "distinct"]
+           "--dim", "65536", "--full", "--no-cpu-baseline", "--no-additional", "--inputs", "distinct"]
     _, line, _ = _run_bench(cmd, tmp_path, timeout=600)
     assert line["verified_reconstruct_equals_sum"] is True
     assert line["config"]["distinct_participants"] == 320 == line["config"]["participants_total"]
     assert "320 distinct participants" in line["verified_against"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_path_computed(gpu, tmp_path):
+    """a plain run (no --full) times the headline and nothing else - no verification, no CPU baseline, no attached workloads -
+    and --dump-outputs writes what its timed path computed: the clerk sums and the shares of the last tile, equal to the
+    oracle's, the same from run to run and the same as in a --full run whose reconstruction verified.  Without --participants,
+    --steps sets the timed work: a step is 5,000 participants of config 3."""
+    import sys
+    from oracle import coracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench_key = bytes((i * 7 + 1) & 0xFF for i in range(32))                 # bench.KEY
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--participants", "8", "--dim", "3000"]
+
+    def dumped(d):
+        out = {}
+        for name in ("clerk_sums", "last_tile_shares"):
+            hi, lo = (np.load(os.path.join(d, f"{name}_{half}.npy")) for half in ("hi31", "lo31"))
+            assert hi.dtype == lo.dtype == np.float64
+            out[name] = hi.astype(np.int64) * (1 << 31) + lo.astype(np.int64)
+        return out
+    line, full, _ = _run_bench(cmd + ["--dump-outputs", str(tmp_path / "a")], tmp_path)
+    assert line["verified_reconstruct_equals_sum"] is None and line["cpu_baseline"] is None and "additional_workloads" not in line
+    assert full["reveal"] is None and full["outputs"]["dir"] == str(tmp_path / "a")
+    assert line["config"]["participants_total"] == 8 and line["steps"] == 2 and line["ms_per_step"] > 0
+    a = dumped(tmp_path / "a")
+    # the oracle: 2 tiles of the same 4 resident participants, tile i on CSPRNG streams 4i .. 4i + 3, systematic share map
+    B = 1000
+    sec = coracle.fill_synthetic(4, 3000, 0, 0x5DA5DA5DA5DA5DA5, P62)
+    tiles = [[coracle.packed_generate_systematic(P62, 3, 1, 8, W[8], W[9], sec[p], coracle.drbg_fill(bench_key, 4 * i + p, B, 1, P62))
+              for p in range(4)] for i in range(2)]
+    sums = np.stack([coracle.combine(P62, np.stack([tiles[i][p][c] for i in range(2) for p in range(4)])) for c in range(8)])
+    assert np.array_equal(a["clerk_sums"], sums.reshape(-1))
+    assert np.array_equal(a["last_tile_shares"], np.stack([np.stack([tiles[1][p][c] for p in range(4)]) for c in range(8)]).reshape(-1))
+    line, _, _ = _run_bench(cmd + ["--full", "--no-cpu-baseline", "--no-additional", "--dump-outputs", str(tmp_path / "b")], tmp_path)
+    assert line["verified_reconstruct_equals_sum"] is True
+    b = dumped(tmp_path / "b")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    line, _, _ = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "0", "--dim", "3000"], tmp_path)
+    assert line["config"]["participants_total"] == 15_000 and line["steps"] == 3 and line["config"]["tile_participants"] == 2500
 
 
 @pytest.mark.parametrize("k,t,n,dim", [(8, 7, 26, 8 * 64 * 5 + 3), (8, 7, 26, 1), (8, 7, 26, 8 * 2048 + 8 * 77), (8, 2, 26, 8 * 300 + 1),

@@ -180,6 +180,37 @@ def test_bench_stdout_line_stays_small_and_carries_the_contract(n_gpus):
     assert json.loads(text) == line                                        # strict JSON
 
 
+def test_bench_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs on the headline's shapes (n = 8, B = 349526; here on a CPU tensor, one participant): the clerk sums whole,
+    a seeded sample of the shares' valid columns (never the row padding), every value exact as float64 halves, the same
+    positions from run to run, and at most 64 MB in all"""
+    import numpy as np
+    import torch
+    bench = _bench()
+    n, P, B, Bs = 8, 1, 349526, 349536
+    rng = np.random.default_rng(3)
+    sums = torch.from_numpy(rng.integers(0, P62, size=(n, B), dtype=np.int64))
+    shares = torch.full((n, P, Bs), -1, dtype=torch.int64)
+    shares[:, :, :B] = torch.from_numpy(rng.integers(0, P62, size=(n, P, B), dtype=np.int64))
+    env = type("Env", (), {"torch": torch, "dev": torch.device("cpu")})()
+    got = {}
+    for run in ("a", "b"):
+        rec = bench.dump_outputs(env, str(tmp_path / run), sums, shares, B)
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == sorted(rec["files"]) == ["clerk_sums_hi31.npy", "clerk_sums_lo31.npy", "last_tile_shares_hi31.npy",
+                                                 "last_tile_shares_lo31.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64_000_000
+        arrs = {f: np.load(tmp_path / run / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        got[run] = {k: arrs[k + "_hi31.npy"].astype(np.int64) * (1 << 31) + arrs[k + "_lo31.npy"].astype(np.int64)
+                    for k in ("clerk_sums", "last_tile_shares")}
+    assert all(np.array_equal(got["a"][k], got["b"][k]) for k in got["a"])
+    assert np.array_equal(got["a"]["clerk_sums"], sums.numpy().reshape(-1))
+    idx = bench._dump_sample(n * P * B, bench.DUMP_SHARES, 1)
+    assert len(idx) == bench.DUMP_SHARES and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["a"]["last_tile_shares"], shares[:, :, :B].reshape(-1).numpy()[idx])
+
+
 def test_bench_emit_refuses_an_oversized_line(tmp_path, capfd):
     bench = _bench()
     full = _fat_record()
