@@ -803,12 +803,21 @@ static int build_n31(sda_share_generator* g) {
     return SDA_OK;
 }
 
+// L31Params.wide of a compiled three-digit shape: 0 = groups of seven + the rest, 1 = one group, 2 = one group in Karatsuba form
+// (three multiply-adds per term, round 6) - each admitted on the constants of both maps (Msys: nullptr when the handle has no
+// systematic map), or the 7 + rest form serves the handle
+static uint32_t l31_group_mode(const std::vector<uint64_t>& Mm, const std::vector<uint64_t>* Msys, uint32_t kt, uint64_t p,
+                               bool no_wide, bool no_karatsuba) {
+    if (no_wide || !l31_wide_group_ok(Mm, kt, p) || (Msys && !l31_wide_group_ok(*Msys, kt, p))) return 0u;
+    if (no_karatsuba || !l31_karatsuba_ok(Mm, kt, p) || (Msys && !l31_karatsuba_ok(*Msys, kt, p))) return 1u;
+    return 2u;
+}
+
 static int build_l31(sda_share_generator* g) {
     SDA_TRY(l31_params(g->mod.m, g->lp));
-    if (g->l31 && packed_l31_three_digit_compiled(g->k, g->t))          // both maps, or the 7 + rest form serves the handle
-        g->lp.wide = !knob(KNOB_NO_WIDE_GROUP) && l31_wide_group_ok(g->Mmont, g->k + g->t, g->mod.m) && (!g->sys_default || l31_wide_group_ok(g->Msys, g->k + g->t, g->mod.m)) ? 1u : 0u;
-        if (g->lp.wide && !knob(KNOB_NO_KARATSUBA) && l31_karatsuba_ok(g->Mmont, g->k + g->t, g->mod.m) && (!g->sys_default || l31_karatsuba_ok(g->Msys, g->k + g->t, g->mod.m)))
-            g->lp.wide = 2u;                                            // three multiply-adds per term (round 6)
+    if (g->l31 && packed_l31_three_digit_compiled(g->k, g->t))
+        g->lp.wide = l31_group_mode(g->Mmont, g->sys_default ? &g->Msys : nullptr, g->k + g->t, g->mod.m, knob(KNOB_NO_WIDE_GROUP) != 0,
+                                    knob(KNOB_NO_KARATSUBA) != 0);
     SDA_TRY(l31_place_matrix(g, g->Mmont, g->matarg, g->d_M));
     if (g->sys_default) SDA_TRY(l31_place_matrix(g, g->Msys, g->matarg_sys, g->d_Msys));
     return SDA_OK;
@@ -1124,11 +1133,21 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
     if (st == SDA_OK) {
         const PathFacts f = path_facts(g, kn);
         const PathChoice c = select_path(g->k, g->t, g->n, g->mod.m, f, kn);
-        snprintf(out, cap, "wide=%s narrow=%s r_bits=%u call20=%s call12=%s injected=%s fused20=%s fused12=%s transform_shape=%d eight_term_ok=%d",
+        // the radix of the limb-31 constants (l31_place_matrix: the global-matrix form follows the run-time rule) and the group
+        // mode a handle would run (build_l31, knobs at their defaults)
+        const unsigned l31_radix = c.wide == WIDE_L31 ? c.l31_r_bits : c.wide == WIDE_L31_GLOBAL ? packed_l31_rt_r_bits(g->k + g->t) : 0u;
+        uint32_t l31_group = 0;
+        if (c.wide == WIDE_L31 && packed_l31_three_digit_compiled(g->k, g->t)) {
+            const bool sys = build_systematic_share_matrix(g->scheme, g->mod.m, g->Msys);
+            l31_group = l31_group_mode(g->Mmont, sys ? &g->Msys : nullptr, g->k + g->t, g->mod.m, false, false);
+        }
+        snprintf(out, cap, "wide=%s narrow=%s r_bits=%u call20=%s call12=%s injected=%s fused20=%s fused12=%s transform_shape=%d eight_term_ok=%d "
+                 "l31_radix=%u l31_group=%u",
                  wide_name(c.wide), narrow_name(c.narrow), c.wide == WIDE_L31 ? c.l31_r_bits : 0u, family_name(path_for_call(c, false, 20)),
                  family_name(path_for_call(c, false, 12)), family_name(path_for_call(c, true, 20)),
                  fused_for_call(c, 20) == FAM_GENERIC ? "none" : family_name(fused_for_call(c, 20)),
-                 fused_for_call(c, 12) == FAM_GENERIC ? "none" : family_name(fused_for_call(c, 12)), (int)f.transform_shape, (int)f.eight_term_ok);
+                 fused_for_call(c, 12) == FAM_GENERIC ? "none" : family_name(fused_for_call(c, 12)), (int)f.transform_shape, (int)f.eight_term_ok,
+                 l31_radix, (unsigned)l31_group);
     }
     sda_share_generator_free(g);
     return st;

@@ -22,6 +22,9 @@ OMEGA = {8: 631229665360524489, 9: 3451275676410824977, 16: 2589100645267092065,
 P31 = 2147482801                                                       # largest prime = 1 mod 432 below 2^31
 TSS_P, TSS_W2, TSS_W3 = 746497, 95660, 610121                          # tss's shipped PSS_155_728_100
 TSS_P2, TSS2_W2, TSS2_W3 = 5038849, 4318906, 1814687                   # tss's shipped PSS_155_19682_100
+P31_MAX, P31_NEXT = (1 << 31) - 1, 2147483659                          # the largest n31 prime and the first prime above 2^31
+NG_MAX, NG_NEXT = 8355691, 8355713                                     # the largest narrow-limb-GEMM prime and the next one
+P_MAX = (1 << 62) - 57                                                 # the largest modulus the library admits
 
 
 @pytest.fixture(scope="module")
@@ -68,8 +71,43 @@ TABLE = [
 ]
 
 
+# the modulus limits (tests/test_extremes_gpu.py; omegas 2 and 3: distinct nodes, no transform structure) - a table of its own
+# because its ids carry the whole modulus (P62 and 2^62 - 57 have the same bit length)
+BOUNDARY_TABLE = [
+    # n31 up to 2^31 - 1 and not one prime further; the narrow limb GEMM up to 8355691 and not at 8355713 (the first prime above 0x7F7F7F)
+    ((3, 1, 8, P31_MAX, 2, 3), ("l31", "n31", 62)),
+    ((8, 7, 26, P31_MAX, 2, 3), ("l31", "n31", 93)),
+    ((12, 3, 26, P31_MAX, 2, 3), ("mfma", "n31", 0)),
+    ((3, 1, 8, P31_NEXT, 2, 3), ("l31", "none", 62)),
+    ((8, 7, 26, P31_NEXT, 2, 3), ("l31", "none", 93)),
+    ((12, 3, 26, P31_NEXT, 2, 3), ("mfma", "none", 0)),
+    ((1, 1, 2, 536870909, 2, 3), ("l31", "n31", 62)),                   # the primes on either side of 2^29 (16 / 4 terms per reduction)
+    ((5, 4, 26, 536870923, 2, 3), ("l31", "n31", 62)),
+    ((20, 13, 50, NG_MAX, 2, 3), ("l31_global", "ngemm", 0)),
+    ((20, 13, 50, NG_NEXT, 2, 3), ("l31_global", "none", 0)),
+    ((300, 211, 728, NG_MAX, 2, 3), ("generic", "ngemm", 0)),
+    ((300, 211, 728, NG_NEXT, 2, 3), ("generic", "none", 0)),
+    # 2^62 - 57, the largest modulus the library admits: 12..16 terms on the limb GEMM, the three-digit limb-31 shapes stay there
+    ((12, 3, 26, P_MAX, 2, 3), ("mfma", "none", 0)),
+    ((16, 0, 26, P_MAX, 2, 3), ("mfma", "none", 0)),
+    ((1, 14, 26, P_MAX, 2, 3), ("mfma", "none", 0)),
+    ((8, 7, 26, P_MAX, 2, 3), ("l31", "none", 93)),
+    ((5, 4, 26, P_MAX, 2, 3), ("l31", "none", 62)),
+    ((20, 13, 80, P_MAX, 2, 3), ("l31_global", "none", 0)),
+]
+
+
 @pytest.mark.parametrize("scheme,want", TABLE, ids=[f"k{s[0]}t{s[1]}n{s[2]}p{s[3].bit_length()}" for s, _ in TABLE])
 def test_selection_table(lib, scheme, want):
+    _check_row(lib, scheme, want)
+
+
+@pytest.mark.parametrize("scheme,want", BOUNDARY_TABLE, ids=[f"k{s[0]}t{s[1]}n{s[2]}p{s[3]}" for s, _ in BOUNDARY_TABLE])
+def test_selection_table_at_the_modulus_limits(lib, scheme, want):
+    _check_row(lib, scheme, want)
+
+
+def _check_row(lib, scheme, want):
     got = select(lib, *scheme)
     assert (got["wide"], got["narrow"], int(got["r_bits"])) == want, got
     # what each kind of call runs follows from the choice: the narrow overlay serves ChaCha20 and injected randomness,
