@@ -67,6 +67,12 @@ int  sda_debug_stream_create(void** stream);
 int  sda_debug_stream_destroy(void* stream);
 int  sda_debug_stream_synchronize(void* stream);
 int  sda_debug_mem_info(size_t* free_bytes, size_t* total_bytes);
+/* Poly1305 with a CHOSEN one-time key, through the sealed-box kernels (sbox_poly_kernel and sbox_final_kernel, unchanged): the
+ * tags of `rows` device messages (row r at d_msgs + r * msg_slot, d_msg_bytes[r] <= max_msg_bytes bytes; buffer and slot
+ * 16-byte aligned) under the `rows` 32-byte keys (r || s) of the HOST array `keys`, written to the HOST array `tags` (16 bytes
+ * a row).  The sealed-box ABI cannot do this: there r and s come out of Salsa20.  Synchronous; for tests/test_sealedbox_extremes_gpu.py. */
+int  sda_debug_poly1305_rows_dev(const unsigned char* keys, const unsigned char* d_msgs, size_t msg_slot,
+                                 const unsigned long long* d_msg_bytes, size_t rows, size_t max_msg_bytes, unsigned char* tags);
 struct sda_sharing_scheme;
 int  sda_debug_select_path(const struct sda_sharing_scheme* scheme, const char* knobs, char* out, size_t cap);
 #ifdef __cplusplus

@@ -351,6 +351,11 @@ hipError_t launch_sealedbox_seal(const uint8_t* d_esk, const uint8_t* d_pks, siz
                                  const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes, size_t rows,
                                  size_t max_msg_bytes, uint8_t* d_boxes, size_t slot, uint64_t* d_row_bytes, SboxState* d_states,
                                  uint32_t* d_partial, hipStream_t s);
+// test only (sda_debug_poly1305_rows_dev): Poly1305 of message r (d_msgs + r * msg_slot, 16-byte aligned) under the one-time key
+// d_keys[32 r .. 32 r + 32) through the production poly / final kernels; tag at d_heads + 48 r + 32, d_head_bytes[r] = length + 48
+hipError_t launch_sealedbox_poly_test(const uint8_t* d_keys, const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes,
+                                      size_t rows, size_t max_msg_bytes, uint8_t* d_heads, uint64_t* d_head_bytes,
+                                      SboxState* d_states, uint32_t* d_partial, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------------
 // out[i] = sum over g < parts of parts[g*part_stride + i]  mod m   (cross-GPU partial sums)

@@ -67,7 +67,8 @@ SBX_HD void fe_cswap(Fe& f, Fe& g, uint32_t b) {
     }
 }
 
-// carry chain on 64-bit limb sums -> |h_i| <= 2^25 (even) / 2^24 (odd) (+ small)
+// carry chain on 64-bit limb sums |h_i| < 2^62 -> h_i in [-2^25, 2^25) (even i) / [-2^24, 2^24) (odd i), except limb 1,
+// which takes the last carry: |h_1| <= 2^24 + 1 (tests/test_sbox_model.py proves these by interval arithmetic)
 SBX_HD void fe_carry(Fe& out, int64_t h[10]) {
     // two interleaved chains (0,1,2,3,4 | 5,6,7,8,9), then the wrap 9 -> 0 and one more step
 #pragma unroll
@@ -77,20 +78,22 @@ SBX_HD void fe_carry(Fe& out, int64_t h[10]) {
             const int bits = fe_bits(i);
             const int64_t c = (h[i] + ((int64_t)1 << (bits - 1))) >> bits;
             h[i + 1] += c;
-            h[i] -= c << bits;
+            h[i] -= c * ((int64_t)1 << bits);               // not c << bits: a left shift of a negative value is undefined before C++20
         }
         const int64_t c9 = (h[9] + ((int64_t)1 << 24)) >> 25;
         h[0] += c9 * 19;
-        h[9] -= c9 << 25;
+        h[9] -= c9 * ((int64_t)1 << 25);
     }
     const int64_t c0 = (h[0] + ((int64_t)1 << 25)) >> 26;
     h[1] += c0;
-    h[0] -= c0 << 26;
+    h[0] -= c0 * ((int64_t)1 << 26);
 #pragma unroll
     for (int i = 0; i < 10; ++i) out.v[i] = (int32_t)h[i];
 }
 
-// h = f * g.  Inputs |f_i|, |g_i| < 2^27 (sums / differences of two carried elements); 64-bit column sums.
+// h = f * g.  Inputs |f_i|, |g_i| <= 113,025,455 = (2^31 - 1) / 19 (2^26.75): 19 g_i must fit int32_t, and the 64-bit column
+// sums then stay below 2^61.6.  The ladders pass sums / differences of two carried elements: |f_i|, |g_i| <= 2^26 (even i),
+// 2^25 + 2 (odd i) - the maxima tests/test_sbox_model.py records over whole ladders; 2^27 would NOT fit.
 SBX_HD void fe_mul(Fe& out, const Fe& f, const Fe& g) {
     int32_t g19[10], f2[10];
 #pragma unroll
@@ -130,7 +133,7 @@ SBX_HD void fe_sq(Fe& out, const Fe& f) {
         }
 #pragma unroll
         for (int j = i + 1; j < 10; ++j) {
-            // 2 f_i f_j, doubled again when both limbs carry 25 bits: the factors go on f_i (2 or 4 f_i fits: |f_i| < 2^26.1)
+            // 2 f_i f_j, doubled again when both limbs carry 25 bits: the factors go on f_i (2 or 4 f_i fits: |f_i| <= 2^26, see fe_mul)
             const bool odd2 = (i & 1) && (j & 1);
             const int32_t a = odd2 ? 2 * f2[i] : f2[i];
             const int k = i + j;
@@ -190,7 +193,7 @@ SBX_HD void fe_to_words(uint32_t w[8], const Fe& f) {
         const int bits = fe_bits(i);
         const int32_t c = h[i] >> bits;
         h[i + 1] += c;
-        h[i] -= c << bits;
+        h[i] -= c * (1 << bits);
     }
     h[9] &= (1 << 25) - 1;
 #pragma unroll
@@ -379,7 +382,8 @@ SBX_HD void p26_clamped_r(P26& r, const uint32_t k[4]) {
     r.v[4] = t3 >> 8;
 }
 
-// h = (a * b) mod 2^130 - 5, partially reduced: limbs < 2^26 (+ a small excess in limb 1).  Inputs: limbs < 2^27.
+// h = (a * b) mod 2^130 - 5, partially reduced: limbs 0, 2, 3, 4 < 2^26, limb 1 < 2^26 + 64.  Inputs: limbs of a < 2^27 + 128
+// (a product plus a piece), limbs of b < 2^26 + 128 (a product); 5 b_i fits uint32_t, the columns stay below 2^58.
 SBX_HD void p26_mul(P26& out, const P26& a, const P26& b) {
     const uint32_t s1 = b.v[1] * 5, s2 = b.v[2] * 5, s3 = b.v[3] * 5, s4 = b.v[4] * 5;
     uint64_t d0 = (uint64_t)a.v[0] * b.v[0] + (uint64_t)a.v[1] * s4 + (uint64_t)a.v[2] * s3 + (uint64_t)a.v[3] * s2 + (uint64_t)a.v[4] * s1;
@@ -400,7 +404,9 @@ SBX_HD void p26_add(P26& h, const P26& a, const P26& b) {
 #pragma unroll
     for (int i = 0; i < 5; ++i) h.v[i] = a.v[i] + b.v[i];
 }
-// limbs of any size below 2^31 -> partially reduced (< 2^26 each, small excess in limb 1)
+// limb 0 of any size, limbs 1 .. 4 <= 2^32 - 64 (each takes a carry of at most 63 BEFORE it is masked) -> limbs < 2^26,
+// except limb 1 <= 2^26 (the wrap carry lands on it after its mask).  On a p26_mul result every limb comes out < 2^26: the
+// wrap carry is 1 only if limb 1 overflowed, and then its masked value is below 64.
 SBX_HD void p26_carry(P26& h) {
     uint32_t c;
     c = h.v[0] >> 26; h.v[0] &= 0x3FFFFFF; h.v[1] += c;

@@ -195,6 +195,31 @@ extern "C" int sda_debug_mem_info(size_t* free_bytes, size_t* total_bytes) {
     HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));
     return SDA_OK;
 }
+// Poly1305 with a chosen r and s: what the sealed-box ABI cannot reach (its one-time keys come out of Salsa20)
+extern "C" int sda_debug_poly1305_rows_dev(const unsigned char* keys, const unsigned char* d_msgs, size_t msg_slot,
+                                           const unsigned long long* d_msg_bytes, size_t rows, size_t max_msg_bytes,
+                                           unsigned char* tags) {
+    if (!keys || !d_msg_bytes || !tags || (max_msg_bytes && !d_msgs)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (msg_slot % 16 || (reinterpret_cast<uintptr_t>(d_msgs) & 15) || msg_slot < max_msg_bytes)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "message rows must be 16-byte aligned and msg_slot >= max_msg_bytes");
+    if (rows == 0) return SDA_OK;
+    SDA_TRY(capi_device_ready());
+    const size_t state_bytes = rows * sizeof(SboxState), partial_bytes = (rows * sbox_regions(max_msg_bytes) * 5 * sizeof(uint32_t) + 15) / 16 * 16;
+    uint8_t* d = nullptr;                                       // states | partial sums | keys | heads | head lengths
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), state_bytes + partial_bytes + rows * (32 + 48 + 8)));
+    uint8_t* d_keys = d + state_bytes + partial_bytes;
+    uint8_t* d_heads = d_keys + rows * 32;
+    hipError_t e = hipMemset(d, 0, state_bytes + partial_bytes + rows * (32 + 48 + 8));
+    if (e == hipSuccess) e = hipMemcpy(d_keys, keys, rows * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = launch_sealedbox_poly_test(d_keys, d_msgs, msg_slot, reinterpret_cast<const uint64_t*>(d_msg_bytes), rows, max_msg_bytes, d_heads,
+                                       reinterpret_cast<uint64_t*>(d_heads + rows * 48), reinterpret_cast<SboxState*>(d),
+                                       reinterpret_cast<uint32_t*>(d + state_bytes), nullptr);
+    if (e == hipSuccess) e = hipMemcpy2D(tags, 16, d_heads + 32, 48, 16, rows, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(SDA_ERR_HIP, "sda_debug_poly1305_rows_dev failed: %s", hipGetErrorString(e));
+    return SDA_OK;
+}
 #endif
 
 // -------------------------------------------------------------------------------------------------

@@ -33,15 +33,8 @@ __device__ __forceinline__ void load_words(uint32_t* w, const uint8_t* p, int n)
     for (int i = 0; i < n; ++i) w[i] = q[i];
 }
 
-// common tail of setup: from the shared X25519 secret and the nonce to the per-box state
-__device__ __forceinline__ void derive_state(SboxState& st, const uint32_t shared[8], const uint32_t nonce[6]) {
-    const uint32_t zero4[4] = {0, 0, 0, 0};
-    uint32_t k[8];
-    hsalsa20(k, shared, zero4);                               // crypto_box_beforenm
-    hsalsa20(st.subkey, k, nonce);                            // XSalsa20: subkey from the first 16 nonce bytes
-    st.n0 = nonce[4]; st.n1 = nonce[5];
-    uint32_t b0[16];
-    salsa20_block(b0, st.subkey, st.n0, st.n1, 0);            // stream bytes 0..31 = the one-time Poly1305 key
+// the Poly1305 part of the per-box state from the 32-byte one-time key (r || s): s and the powers of the clamped r
+__device__ __forceinline__ void derive_poly_state(SboxState& st, const uint32_t b0[8]) {
     P26 r, rp;
     p26_clamped_r(r, b0);
 #pragma unroll
@@ -57,6 +50,18 @@ __device__ __forceinline__ void derive_state(SboxState& st, const uint32_t share
     for (int s = kPolySteps; s > 1; s >>= 1) { P26 t; p26_mul(t, rp, rp); rp = t; }     // (r^64)^16 = r^1024
 #pragma unroll
     for (int j = 0; j < 5; ++j) st.rS[j] = rp.v[j];
+}
+
+// common tail of setup: from the shared X25519 secret and the nonce to the per-box state
+__device__ __forceinline__ void derive_state(SboxState& st, const uint32_t shared[8], const uint32_t nonce[6]) {
+    const uint32_t zero4[4] = {0, 0, 0, 0};
+    uint32_t k[8];
+    hsalsa20(k, shared, zero4);                               // crypto_box_beforenm
+    hsalsa20(st.subkey, k, nonce);                            // XSalsa20: subkey from the first 16 nonce bytes
+    st.n0 = nonce[4]; st.n1 = nonce[5];
+    uint32_t b0[16];
+    salsa20_block(b0, st.subkey, st.n0, st.n1, 0);            // stream bytes 0..31 = the one-time Poly1305 key
+    derive_poly_state(st, b0);
     uint32_t any = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) any |= shared[i];
@@ -286,7 +291,7 @@ __global__ __launch_bounds__(kSbThreads) void sbox_poly_kernel(const uint8_t* __
         for (int j = 0; j < 5; ++j) wgt.v[j] = st.rpow[lane][j];             // r^(lane+1)
         p26_mul(t, h, wgt);
         h = t;
-        p26_carry(h);                                                        // limbs < 2^26: 64 of them sum below 2^32
+        p26_carry(h);                                                        // of a p26_mul result: limbs <= 2^26 - 1, 64 of them sum to <= 2^32 - 64
     }
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -327,7 +332,7 @@ __global__ __launch_bounds__(64) void sbox_final_kernel(const uint32_t* __restri
             p26_mul(t, acc, RS);
 #pragma unroll
             for (int j = 0; j < 5; ++j) p.v[j] = partial[(r * regions + g) * 5 + j];
-            p26_carry(p);
+            p26_carry(p);                                      // lane sums <= 2^32 - 64 + a carry <= 63: fits with no margin
             p26_add(acc, t, p);
         }
         p26_finish(tag, acc, st.s);
@@ -425,6 +430,33 @@ hipError_t launch_sealedbox_seal(const uint8_t* d_esk, const uint8_t* d_pks, siz
         return e;
     sbox_final_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_partial, sbox_regions(max_msg_bytes), d_states, d_boxes, slot,
                                                                            d_msg_bytes, 0, max_msg_bytes, rows, 1, d_row_bytes, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+// ---- test only (include/sda_hip_debug.h: sda_debug_poly1305_rows_dev; not reachable from the release library) --------
+// Poly1305 of caller-given messages under caller-given one-time keys through the production poly and final kernels: the
+// state a box would get from Salsa20 is filled from the key instead (one lane per row).
+__global__ __launch_bounds__(64) void sbox_setup_poly_test_kernel(const uint8_t* __restrict__ keys, size_t rows, SboxState* __restrict__ states) {
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    uint32_t k[8];
+    load_words(k, keys + 32 * r, 8);
+    derive_poly_state(states[r], k);
+    states[r].bad = 0;
+}
+
+// tag of row r at d_heads + r * 48 + 32 (where a box of slot 48 keeps it), d_head_bytes[r] = message length + 48
+hipError_t launch_sealedbox_poly_test(const uint8_t* d_keys, const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes,
+                                      size_t rows, size_t max_msg_bytes, uint8_t* d_heads, uint64_t* d_head_bytes,
+                                      SboxState* d_states, uint32_t* d_partial, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    sbox_setup_poly_test_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_keys, rows, d_states);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = bulk(nullptr, 0, 0, nullptr, 0, 0, d_msgs, msg_slot, 0, d_msg_bytes, 0, rows, max_msg_bytes, d_states, d_partial,
+                            kPassPoly, 0, s))
+        return e;
+    sbox_final_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_partial, sbox_regions(max_msg_bytes), d_states, d_heads, 48,
+                                                                           d_msg_bytes, 0, max_msg_bytes, rows, 1, d_head_bytes, nullptr, nullptr);
     return hipGetLastError();
 }
 
