@@ -599,6 +599,20 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *   keys) is shared by all calls, so two calls through one handle on different streams race - use one handle per stream.
  *   All rows and slots 16-byte aligned; max_* bound the longest row (they size the launch).  The host forms stage one
  *   payload through the device (ShareEncryptor::encrypt / ShareDecryptor::decrypt minus the varint codec).
+ *
+ *   sda_share_combiner_update_sealed_rows_dev : clerk.rs:78-86 without the plaintext.  A sibling of
+ *                   sda_share_combiner_update_varint_rows_dev (between begin_dev with jobs == 1 and finish_dev; any number
+ *                   of calls per job, freely mixed with the other update forms) that takes the rows while they are still
+ *                   sealed boxes, laid out as for open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does
+ *                   (d_ok[r] when d_ok is given; *d_status |= 16 for a box that does not authenticate, is shorter than 48
+ *                   or longer than max_box_bytes bytes, or has an all-zero shared secret).  Step 2 streams the rows that
+ *                   passed ONCE: keystream, varint decode and the sums of the `dimension` columns in one kernel, the decrypted
+ *                   bytes never leave registers and LDS - no plaintext buffer, no second copy of the job in HBM.  A row that
+ *                   failed step 1 adds nothing.  The sums after finish_dev and bit 16 of *d_status equal those of
+ *                   open_rows_dev + update_varint_rows_dev; for a job whose boxes all authenticate so does the whole status
+ *                   word (1 over-long value, 2 wrong count, 4 unterminated).  THE REFERENCE FAILS THE WHOLE JOB on one bad
+ *                   box ("Sodium decryption failure", sodium.rs:78-80): check *d_status before using finish_dev's output.
+ *                   Uses the sealed-box handle's scratch: the one-stream-at-a-time rule above holds for this call too.
  * ============================================================================================= */
 #define SDA_SEALBYTES 48
 typedef struct sda_sealedbox sda_sealedbox_t;
@@ -618,6 +632,10 @@ int  sda_sealedbox_seal(sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t*
                         const uint8_t* msg, size_t len, uint8_t* out, size_t out_cap);
 int  sda_sealedbox_open(sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* box, size_t len,
                         uint8_t* out, size_t out_cap, size_t* out_len);
+int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                               const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
+                                               size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
+                                               uint32_t* d_ok /* optional */, uint32_t* d_status, void* stream);
 
 /* =============================================================================================
  * Cross-GPU modular reduction (new; no reference counterpart - SURVEY.md 8e: the reference's parties meet over HTTP).

@@ -296,6 +296,43 @@ class ShareCombiner(_Handle):
         check(self._lib.sda_share_combiner_update_varint_rows_dev(self._h, codec._h, d_bytes, slot_bytes, d_row_bytes,
                                                                   rows, d_status, stream or None))
 
+    def update_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", pk: bytes, sk: bytes, d_boxes: int,
+                               slot_bytes: int, d_row_bytes: int, rows: int, max_box_bytes: int, d_status: int, d_ok: int = 0,
+                               stream: int = 0) -> None:
+        """rows that are still sealed boxes (the SDAJOBv1 SEALED layout): tags verified, then decrypted, decoded and summed
+        in one pass - no plaintext buffer.  *d_status & 16: some box failed, the sums must not be used (sodium.rs:78-80)"""
+        check(self._lib.sda_share_combiner_update_sealed_rows_dev(self._h, codec._h, box._h, pk, sk, d_boxes, slot_bytes,
+                                                                  d_row_bytes, rows, max_box_bytes, d_ok or None, d_status,
+                                                                  stream or None))
+
+    def combine_sealed_job(self, blob, pk: bytes, sk: bytes, dimension: int) -> np.ndarray:
+        """clerk.rs:78-86 for an SDAJOBv1 blob of sealed boxes: open every encryption, decode it, sum the share vectors.
+        One bad box fails the job ("Sodium decryption failure"), so does a payload that does not hold `dimension` shares
+        ("Wrong dimension")."""
+        from .device import DeviceBuffer, DeviceBytes
+        job = JobContainer.parse(bytes(blob))
+        L = job.layout
+        if L.payload_kind != capi.JOB_SEALED:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "combine_sealed_job needs a job of sealed boxes (payload kind SEALED)")
+        if L.rows == 0:
+            return np.zeros(0, dtype=np.int64)                       # combiner.rs:17
+        d_job = DeviceBytes.from_bytes(job.blob)
+        d_status = DeviceBuffer(1).zero()
+        d_sums = DeviceBuffer(max(dimension, 1))
+        codec, box = VarintCodec(), SealedBox()
+        self.begin_dev(1, dimension)
+        self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes, d_job.ptr + L.lengths_offset,
+                                    L.rows, L.slot_bytes, d_status.ptr)
+        self.finish_dev(d_sums.ptr)
+        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
+        if status & 16:
+            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
+        if status & 2:
+            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")                    # combiner.rs:21
+        if status:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        return d_sums.to_numpy()[:dimension].copy()
+
     def set_residency(self, max_workgroups_per_cu: int) -> None:
         check(self._lib.sda_share_combiner_set_residency(self._h, max_workgroups_per_cu))
 

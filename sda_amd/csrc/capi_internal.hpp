@@ -7,6 +7,12 @@
 int capi_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets sda_last_error(), returns code
 int capi_make_mod(int64_t modulus, sda::ModParams& mod);                                  // validated Barrett / Lemire constants
 int capi_device_ready();                                                                  // a device exists; make the selected one current
+// first half of a sealed-box open on the handle's scratch (sda_sealedbox.cpp): every tag verified, d_ok / *d_status |= 16 /
+// SboxState.bad written as sda_sealedbox_open_rows_dev writes them, NO keystream pass.  *d_states: the per-row states.
+struct sda_sealedbox;
+int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot_bytes,
+                               const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status,
+                               int device, hipStream_t s, const sda::SboxState** d_states);
 
 // ---- path-selection knobs (A/B measurements and parity tests of the non-default kernels) -----------------------------------
 // A release build of the library reads NO environment variable: a knob changes only through the test-only entry point
@@ -16,7 +22,8 @@ namespace sda {
 enum Knob {
     KNOB_FORCE_GENERIC, KNOB_FORCE_MONT64, KNOB_FORCE_FFT, KNOB_FORCE_MFMA, KNOB_NO_MFMA, KNOB_NO_SIDE_STREAM,
     KNOB_SIDE_STREAM_WGS, KNOB_SIDE_STREAM_PRIORITY_HIGH, KNOB_FFT_G, KNOB_FFT_THREADS, KNOB_VARINT_PATH /* 1 stream, 2 scan */,
-    KNOB_FORCE_COLLECTIVES, KNOB_NO_NARROW, KNOB_WIRE_WG_PER_CU, KNOB_SBOX_WG_PER_CU, KNOB_NO_LAZY, KNOB_NO_XCD_MAP, KNOB_NO_NGEMM, KNOB_NO_WIDE_GROUP, KNOB_NGEMM_CLERK_WG, KNOB_NO_KARATSUBA, KNOB_COUNT
+    KNOB_FORCE_COLLECTIVES, KNOB_NO_NARROW, KNOB_WIRE_WG_PER_CU, KNOB_SBOX_WG_PER_CU, KNOB_NO_LAZY, KNOB_NO_XCD_MAP, KNOB_NO_NGEMM, KNOB_NO_WIDE_GROUP, KNOB_NGEMM_CLERK_WG, KNOB_NO_KARATSUBA,
+    KNOB_SEALED_WAVES /* 16: the wide instance */, KNOB_COUNT
 };
 long knob(Knob k);             // 0 = unset / default
 // an UNUSED dynamic-LDS request that caps the resident workgroups of a launch at wg_per_cu per CU (0: no cap), so that a

@@ -316,6 +316,13 @@ hipError_t launch_varint_stream_encode(const VarintRows& R, uint8_t* d_out, size
 hipError_t launch_varint_stream_combine(const uint8_t* d_bytes, size_t n_bytes, const RowRanges& rr, size_t jobs,
                                         size_t rows_per_job, size_t len, uint64_t* d_acc_lo, int64_t* d_acc_hi,
                                         uint32_t* d_status, hipStream_t s);
+// the same sums from rows that are still sealed boxes (box r at d_boxes + r * slot, d_row_bytes[r] bytes) whose tags
+// launch_sealedbox_verify has checked: rows marked bad in d_states are skipped, the others are decrypted in registers.
+// One job; *waves = rows per workgroup of the instance launched (8; 16 only through the A/B knob)
+struct SboxState;
+hipError_t launch_sealed_stream_combine(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
+                                        size_t max_box_bytes, const SboxState* d_states, size_t len, uint64_t* d_acc_lo,
+                                        int64_t* d_acc_hi, uint32_t* d_status, hipStream_t s, int* waves);
 hipError_t launch_varint_rowcheck(const uint8_t* d_bytes, size_t n_bytes, const uint64_t* d_offsets, size_t rows,
                                   size_t len, const uint64_t* d_block_val_off, uint32_t* d_status, hipStream_t s);
 
@@ -346,6 +353,11 @@ hipError_t launch_sealedbox_open(const uint8_t pk[32], const uint8_t sk[32], con
                                  const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint8_t* d_out, size_t out_slot,
                                  uint64_t* d_out_bytes, uint32_t* d_ok, uint32_t* d_status, SboxState* d_states,
                                  uint32_t* d_partial, hipStream_t s);
+// the first half of launch_sealedbox_open: setup, Poly1305, tag compare (d_out_bytes[r] = message length, 0 for a box that fails;
+// d_states[r].bad set on such rows) - and no keystream pass
+hipError_t launch_sealedbox_verify(const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot,
+                                   const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint64_t* d_out_bytes,
+                                   uint32_t* d_ok, uint32_t* d_status, SboxState* d_states, uint32_t* d_partial, hipStream_t s);
 // message r at d_msgs + r * msg_slot sealed to d_pks[(r / rows_per_key) % n_pks] with the ephemeral secret d_esk[r]
 hipError_t launch_sealedbox_seal(const uint8_t* d_esk, const uint8_t* d_pks, size_t n_pks, size_t rows_per_key,
                                  const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes, size_t rows,

@@ -13,7 +13,7 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define SBX_HD __host__ __device__ __forceinline__
-#define SBX_HD_NOINLINE __host__ __device__ __noinline__
+#define SBX_HD_NOINLINE inline __host__ __device__ __noinline__      // inline: one definition however many files include this
 #else
 #define SBX_HD inline
 #define SBX_HD_NOINLINE inline

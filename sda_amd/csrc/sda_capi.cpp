@@ -110,7 +110,8 @@ namespace {
 const char* const kKnobNames[sda::KNOB_COUNT] = {
     "SDA_FORCE_GENERIC", "SDA_FORCE_MONT64", "SDA_FORCE_FFT", "SDA_FORCE_MFMA", "SDA_NO_MFMA", "SDA_NO_SIDE_STREAM",
     "SDA_SIDE_STREAM_WGS", "SDA_SIDE_STREAM_PRIORITY", "SDA_FFT_G", "SDA_FFT_THREADS", "SDA_VARINT_PATH", "SDA_FORCE_COLLECTIVES",
-    "SDA_NO_NARROW", "SDA_WIRE_WG_PER_CU", "SDA_SBOX_WG_PER_CU", "SDA_NO_LAZY", "SDA_NO_XCD_MAP", "SDA_NO_NGEMM", "SDA_NO_WIDE_GROUP", "SDA_NGEMM_CLERK_WG", "SDA_NO_KARATSUBA"};
+    "SDA_NO_NARROW", "SDA_WIRE_WG_PER_CU", "SDA_SBOX_WG_PER_CU", "SDA_NO_LAZY", "SDA_NO_XCD_MAP", "SDA_NO_NGEMM", "SDA_NO_WIDE_GROUP", "SDA_NGEMM_CLERK_WG", "SDA_NO_KARATSUBA",
+    "SDA_SEALED_WAVES"};
 std::atomic<long> g_knobs[sda::KNOB_COUNT];
 }  // namespace
 long sda::knob(sda::Knob k) {
@@ -2467,6 +2468,34 @@ extern "C" int sda_share_combiner_update_varint_rows_dev(sda_share_combiner_t* c
                                          c->acc.hi.as<int64_t>(), d_status, c->ctx.pick(stream)));
     if (L == 0) HIP_TRY(launch_varint_stream_decode(d_bytes, rows * slot_bytes, rr, rows, 0, 0, nullptr, d_status, c->ctx.pick(stream)));
     return c->mark_pending(c->ctx.pick(stream));
+}
+
+// a clerking job straight from its sealed boxes (clerk.rs:78-86): verify every tag, then ONE pass that decrypts, decodes and sums
+extern "C" int sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                         const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
+                                                         size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows,
+                                                         size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status, void* stream) {
+    if (!c || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c->begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    if (c->jobs != 1) return fail(SDA_ERR_STATE, "the sealed form feeds ONE job: the combiner was begun with %zu jobs", c->jobs);
+    if (rows == 0) return SDA_OK;
+    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
+    SDA_TRY(c->ctx.use());
+    hipStream_t s = c->ctx.pick(stream);
+    const SboxState* d_states = nullptr;
+    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, c->ctx.device, s,
+                                       &d_states));
+    SDA_TRY(c->join_pending(s));
+    int waves = 0;
+    HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, c->dimension,
+                                         c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_status, s, &waves));
+    note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);      // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return c->mark_pending(s);
 }
 
 extern "C" int sda_share_combiner_update_varint(sda_share_combiner_t* c, sda_varint_codec_t* codec, const uint8_t* bytes,

@@ -22,6 +22,7 @@ struct sda_sealedbox {
     void* d_partial = nullptr; size_t partial_cap = 0;     // Poly1305 partial sums
     void* d_keys = nullptr; size_t keys_cap = 0;           // ephemeral secrets + recipient keys (seal)
     void* d_io = nullptr; size_t io_cap = 0;               // host-form staging
+    void* d_lens = nullptr; size_t lens_cap = 0;           // message lengths of a verify-only pass (nobody reads them)
 };
 
 namespace {
@@ -68,9 +69,9 @@ extern "C" int sda_sealedbox_new(sda_sealedbox_t** out) {
 extern "C" void sda_sealedbox_free(sda_sealedbox_t* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    void* bufs[4] = {b->d_states, b->d_partial, b->d_keys, b->d_io};
-    size_t caps[4] = {b->states_cap, b->partial_cap, b->keys_cap, b->io_cap};
-    for (int i = 0; i < 4; ++i)
+    void* bufs[5] = {b->d_states, b->d_partial, b->d_keys, b->d_io, b->d_lens};
+    size_t caps[5] = {b->states_cap, b->partial_cap, b->keys_cap, b->io_cap, b->lens_cap};
+    for (int i = 0; i < 5; ++i)
         if (bufs[i]) { (void)hipMemset(bufs[i], 0, caps[i]); (void)hipFree(bufs[i]); }      // key-derived material: wiped
     delete b;
 }
@@ -93,6 +94,20 @@ extern "C" int sda_sealedbox_open_rows_dev(sda_sealedbox_t* b, const uint8_t pk[
                                          d_ok, d_status, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial),
                                          reinterpret_cast<hipStream_t>(stream));
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box open launch failed: %s", hipGetErrorString(e));
+}
+
+// for sda_share_combiner_update_sealed_rows_dev (sda_capi.cpp), which has checked the arguments
+int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot_bytes,
+                               const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status,
+                               int device, hipStream_t s, const SboxState** d_states) {
+    const size_t max_msg = max_box_bytes > SDA_SEALBYTES ? max_box_bytes - SDA_SEALBYTES : 0;
+    if (b->device != device) return capi_fail(SDA_ERR_INVALID_ARGUMENT, "the sealed-box handle lives on device %d, the combiner on device %d", b->device, device);
+    if (int st = scratch(b, rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
+    hipError_t e = launch_sealedbox_verify(pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, static_cast<uint64_t*>(b->d_lens),
+                                           d_ok, d_status, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
+    *d_states = static_cast<const SboxState*>(b->d_states);
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box verify launch failed: %s", hipGetErrorString(e));
 }
 
 extern "C" int sda_sealedbox_seal_rows_dev(sda_sealedbox_t* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key,

@@ -392,10 +392,9 @@ static hipError_t bulk(const uint8_t* d_in, size_t in_slot, size_t in_off, uint8
     return hipSuccess;
 }
 
-hipError_t launch_sealedbox_open(const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot,
-                                 const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint8_t* d_out, size_t out_slot,
-                                 uint64_t* d_out_bytes, uint32_t* d_ok, uint32_t* d_status, SboxState* d_states,
-                                 uint32_t* d_partial, hipStream_t s) {
+hipError_t launch_sealedbox_verify(const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot,
+                                   const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint64_t* d_out_bytes,
+                                   uint32_t* d_ok, uint32_t* d_status, SboxState* d_states, uint32_t* d_partial, hipStream_t s) {
     if (rows == 0) return hipSuccess;
     const size_t max_msg = max_box_bytes > 48 ? max_box_bytes - 48 : 0;
     SboxKeyArg apk = key_arg(pk), ask = key_arg(sk);
@@ -405,13 +404,24 @@ hipError_t launch_sealedbox_open(const uint8_t pk[32], const uint8_t sk[32], con
     if (hipError_t e = hipGetLastError()) return e;
     // verify, THEN decrypt: the tag of every box is checked before the keystream pass runs, and that pass skips the rows that
     // failed - no unauthenticated plaintext ever reaches d_out (crypto_box_seal_open writes nothing on failure either)
-    if (hipError_t e = bulk(d_boxes, slot, 48, d_out, out_slot, 0, d_boxes, slot, 48, d_row_bytes, 48, rows, max_msg, d_states,
+    if (hipError_t e = bulk(d_boxes, slot, 48, nullptr, 0, 0, d_boxes, slot, 48, d_row_bytes, 48, rows, max_msg, d_states,
                             d_partial, kPassPoly, 0, s))
         return e;
     sbox_final_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_partial, sbox_regions(max_msg), d_states,
                                                                            const_cast<uint8_t*>(d_boxes), slot, d_row_bytes, 48, max_msg, rows, 0,
                                                                            d_out_bytes, d_ok, d_status);
-    if (hipError_t e = hipGetLastError()) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_sealedbox_open(const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot,
+                                 const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint8_t* d_out, size_t out_slot,
+                                 uint64_t* d_out_bytes, uint32_t* d_ok, uint32_t* d_status, SboxState* d_states,
+                                 uint32_t* d_partial, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const size_t max_msg = max_box_bytes > 48 ? max_box_bytes - 48 : 0;
+    if (hipError_t e = launch_sealedbox_verify(pk, sk, d_boxes, slot, d_row_bytes, rows, max_box_bytes, d_out_bytes, d_ok, d_status,
+                                               d_states, d_partial, s))
+        return e;
     return bulk(d_boxes, slot, 48, d_out, out_slot, 0, d_boxes, slot, 48, d_row_bytes, 48, rows, max_msg, d_states, d_partial,
                 kPassStream, 0, s);
 }

@@ -15,6 +15,7 @@
 #include "capi_internal.hpp"
 #include "kernels.hpp"
 #include "modarith.hpp"
+#include "sbox_primitives.hpp"
 
 namespace sda {
 
@@ -428,10 +429,18 @@ __device__ __forceinline__ int64_t tile_value(const uint32_t* tile32, int start,
     return (int64_t)((x >> 1) ^ (uint64_t)(-(int64_t)(x & 1)));         // zig-zag
 }
 
+// What a RowStream does to a chunk between the load and the decode.  The rows of the plaintext kernels are what they are:
+struct PlainBytes {
+    __device__ __forceinline__ void begin_group(uint64_t) {}
+    __device__ __forceinline__ void apply(uint4&, int, bool) const {}
+};
+
 // A row being streamed by one wave.  next_group() decodes up to kStreamDepth chunks and hands every value to
 // sink(column, value); the state between calls is the column index, the continuation bitmap of the last 16 bytes,
-// the halo in the wave's LDS tile and the prefetched chunks.
-struct RowStream {
+// the halo in the wave's LDS tile and the prefetched chunks.  Crypt: PlainBytes, or the XSalsa20 keystream of a sealed
+// box (XSalsaBytes below), xor-ed into the chunk while it is in registers.
+template <class Crypt>
+struct RowStreamT {
     const uint8_t* bytes;
     int64_t rel0, end_rel;            // this lane's byte offset in chunk 0; end of the row
     int lo0;                          // bytes of this lane that precede the row in chunk 0 (0..16)
@@ -439,6 +448,7 @@ struct RowStream {
     uint32_t carry_prev, flags;
     uint32_t* tile32;
     uint4 w[kStreamDepth];
+    Crypt crypt;
 
     __device__ __forceinline__ void open(const uint8_t* __restrict__ bytes_, uint64_t a, uint64_t b, uint64_t len_, uint8_t* tile) {
         const int lane = threadIdx.x & 63;
@@ -460,6 +470,7 @@ struct RowStream {
     template <class Sink>
     __device__ __forceinline__ void next_group(Sink&& sink) {
         const int lane = threadIdx.x & 63;
+        crypt.begin_group(j0);
 #pragma unroll
         for (int d = 0; d < kStreamDepth; ++d) {
             const uint64_t j = j0 + d;
@@ -473,6 +484,7 @@ struct RowStream {
             __builtin_amdgcn_sched_barrier(0);
             w[d] = stream_load(bytes, rel0 + (int64_t)(j + kStreamDepth) * 1024, end_rel);
             __builtin_amdgcn_sched_barrier(0);
+            crypt.apply(cur, d, rel0 + (int64_t)j * 1024 < end_rel);   // the 0x80 fill past the row is not ciphertext
             uint32_t own = cont_bits16(cur), terms = ~own & 0xFFFFu;
             if (j == 0 || j + 1 >= n_chunks) {                    // wave-uniform: only the edge chunks hold foreign bytes
                 const int64_t q = rel0 + (int64_t)j * 1024;
@@ -520,6 +532,8 @@ struct RowStream {
         if (flags) atomicOr(status, flags);
     }
 };
+
+using RowStream = RowStreamT<PlainBytes>;
 
 struct StoreSink {
     int64_t* row;
@@ -707,6 +721,32 @@ struct WindowSink {
     }
 };
 
+// After a group: the columns below min(current column of the workgroup's rows) can no longer be touched - fold them and add
+// them to the global accumulators, slide the window.  Called by every thread after cols[] is written and a barrier; true = every
+// row is through.  Shared by the plaintext and the sealed kernel.
+template <int kCombWaves>
+__device__ __forceinline__ bool window_flush(unsigned long long* lo32, unsigned long long* hi32, WindowSink& sink, const uint64_t* cols,
+                                             uint64_t len) {
+    uint64_t nb = len;
+#pragma unroll
+    for (int w = 0; w < kCombWaves; ++w) nb = cols[w] < nb ? cols[w] : nb;
+    // every later value has column >= nb: fold and flush [base, nb)
+    uint64_t end = nb < sink.base + kCombWindow ? nb : sink.base + kCombWindow;
+    for (uint64_t c = sink.base + threadIdx.x; c < end; c += kCombWaves * 64) {
+        const uint32_t i = (uint32_t)c & (kCombWindow - 1);
+        const uint64_t A = lo32[i];
+        const int64_t Bq = (int64_t)hi32[i];
+        if (A | (uint64_t)Bq) {
+            lo32[i] = 0; hi32[i] = 0;
+            const uint64_t lo = A + ((uint64_t)Bq << 32);
+            acc_atomic_add(sink.acc_lo + c, sink.acc_hi + c, lo, (Bq >> 32) + (lo < A ? 1 : 0));
+        }
+    }
+    sink.base = nb;
+    __syncthreads();
+    return nb >= len;
+}
+
 template <int kCombWaves>       // rows per workgroup: 16 (one pair of global atomics per column and 16 rows), 8 when rows are few
 __global__ __launch_bounds__(kCombWaves * 64) void varint_stream_combine_kernel(
     const uint8_t* __restrict__ bytes, uint64_t n_bytes, RowRanges offsets, uint64_t rows_per_job,
@@ -735,24 +775,118 @@ __global__ __launch_bounds__(kCombWaves * 64) void varint_stream_combine_kernel(
         }
         if ((threadIdx.x & 63) == 0) cols[wave] = live ? rs.col : len;     // a finished row no longer holds the window
         __syncthreads();
-        uint64_t nb = len;
+        if (window_flush<kCombWaves>(lo32, hi32, sink, cols, len)) break;     // all 16 rows are through
+    }
+}
+
+// ---- sealed boxes -> clerk sums without the plaintext (clerk.rs:78-86 in one pass over the ciphertext) -----------------
+// The same kernel over rows that are still XSalsa20 ciphertext: row r is the payload of the sealed box at
+// boxes + r * slot (epk 32 | tag 16 | ciphertext), whose tag the sealed-box verify pass has ALREADY checked - a row whose
+// state says `bad` is not streamed, so no byte decrypted from an unauthenticated box reaches an accumulator.  The
+// keystream is xor-ed into a chunk while it sits in registers; decrypted bytes exist in registers and LDS only.
+//
+// Geometry: the ciphertext starts at box offset 48 (16-byte aligned), message byte m is stream byte 32 + m (stream bytes
+// 0..31 are the Poly1305 key), so lane l of chunk j holds the 16-byte stream piece 2 + 64 j + l and a group of
+// kStreamDepth = 4 chunks spans the Salsa20 blocks 64 g (second half) .. 64 g + 64 (first half).  Per group lane l
+// computes block 64 g + 1 + l into slot 1 + l of the wave's keystream tile; slot 0 is the previous group's slot 64
+// (block 0 at open).  The tile is transposed ([word][slot]) so that the stores are lane-contiguous, with a slot stride
+// of 66 words: the four pieces of a block are then 8 banks apart (4 * 66 = 8 mod 32) and the 32 lanes of a
+// ds_read_b32 group - eight slots, four pieces each - fall on 32 different banks.
+static constexpr int kKsStride = 66;
+static constexpr int kKsTile = 16 * kKsStride;              // words per wave
+
+struct XSalsaBytes {
+    uint32_t key[8], n0, n1;                               // wave-uniform: the box's XSalsa20 subkey and nonce tail
+    uint32_t* ks;
+    __device__ __forceinline__ void open(const SboxState& st, uint32_t* tile) {
+        const int lane = threadIdx.x & 63;
 #pragma unroll
-        for (int w = 0; w < kCombWaves; ++w) nb = cols[w] < nb ? cols[w] : nb;
-        // every later value has column >= nb: fold and flush [base, nb)
-        uint64_t end = nb < sink.base + kCombWindow ? nb : sink.base + kCombWindow;
-        for (uint64_t c = sink.base + threadIdx.x; c < end; c += kCombWaves * 64) {
-            const uint32_t i = (uint32_t)c & (kCombWindow - 1);
-            const uint64_t A = lo32[i];
-            const int64_t Bq = (int64_t)hi32[i];
-            if (A | (uint64_t)Bq) {
-                lo32[i] = 0; hi32[i] = 0;
-                const uint64_t lo = A + ((uint64_t)Bq << 32);
-                acc_atomic_add(sink.acc_lo + c, sink.acc_hi + c, lo, (Bq >> 32) + (lo < A ? 1 : 0));
+        for (int i = 0; i < 8; ++i) key[i] = st.subkey[i];
+        n0 = st.n0; n1 = st.n1;
+        ks = tile;
+        // (wave-uniform inputs: all 64 lanes compute the same block and one stores it - once per row, against one block per
+        // lane and group in the stream; likewise byte_at below)
+        uint32_t b[16];
+        sbx::salsa20_block(b, key, n0, n1, 0);             // block 0 into slot 64: the first group's carry moves it to slot 0
+        if (lane == 0) {
+#pragma unroll
+            for (int w = 0; w < 16; ++w) ks[w * kKsStride + 64] = b[w];
+        }
+    }
+    __device__ __forceinline__ void begin_group(uint64_t j0) {
+        const int lane = threadIdx.x & 63;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the previous group's reads are done, open()'s store is in
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 16) ks[lane * kKsStride] = ks[lane * kKsStride + 64];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t b[16];
+        sbx::salsa20_block(b, key, n0, n1, 16 * j0 + 1 + (uint64_t)lane);   // j0 = 4 g
+#pragma unroll
+        for (int w = 0; w < 16; ++w) ks[w * kKsStride + 1 + lane] = b[w];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void apply(uint4& cur, int d, bool ciphertext) const {
+        const uint32_t p = 2u + 64u * (uint32_t)d + (threadIdx.x & 63u);    // stream piece inside the group
+        const uint32_t* k = ks + (p & 3u) * 4u * kKsStride + (p >> 2);
+        if (ciphertext) {
+            cur.x ^= k[0]; cur.y ^= k[kKsStride]; cur.z ^= k[2 * kKsStride]; cur.w ^= k[3 * kKsStride];
+        }
+    }
+    // one decrypted message byte (wave-uniform m): the row's last byte decides "unterminated" before the row is streamed
+    __device__ __forceinline__ uint32_t byte_at(uint8_t c, uint64_t m) const {
+        const uint64_t sp = m + 32;
+        uint32_t b[16];
+        sbx::salsa20_block(b, key, n0, n1, sp >> 6);
+        uint32_t word = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) word = ((uint32_t)(sp >> 2) & 15u) == (uint32_t)w ? b[w] : word;
+        return (c ^ (word >> (8 * (uint32_t)(sp & 3)))) & 0xFFu;
+    }
+};
+
+template <int kCombWaves>
+__global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_combine_kernel(
+    const uint8_t* __restrict__ boxes, uint64_t slot, const uint64_t* __restrict__ row_bytes, uint64_t max_box,
+    const SboxState* __restrict__ states, uint64_t rows, uint64_t len, uint64_t* __restrict__ acc_lo,
+    int64_t* __restrict__ acc_hi, uint32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kCombWaves][kStreamTile];
+    __shared__ uint32_t kstream[kCombWaves][kKsTile];
+    __shared__ unsigned long long lo32[kCombWindow], hi32[kCombWindow];
+    __shared__ uint64_t cols[kCombWaves];
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+    const uint64_t r = (uint64_t)blockIdx.x * kCombWaves + wave;
+    for (int i = threadIdx.x; i < kCombWindow; i += kCombWaves * 64) { lo32[i] = 0; hi32[i] = 0; }
+    RowStreamT<XSalsaBytes> rs;
+    bool live = false;
+    if (r < rows) {
+        const uint64_t have = row_bytes[r];
+        // a box the verify pass refused (tag, length, all-zero shared secret) carries `bad`; the length is tested again here
+        // so that the row can never leave its slot whatever the state says
+        if (have >= 48 && have <= max_box && have <= slot && !states[r].bad) {
+            const uint64_t a = r * slot + 48, b = r * slot + have;
+            // the verdicts of stream_row_range on the plaintext this row would have been opened to
+            if (len == 0) { if (a != b && lead) atomicOr(status, SDA_VARINT_ROW_COUNT); }
+            else if (a == b) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); }
+            else {
+                rs.crypt.open(states[r], kstream[wave]);
+                if (rs.crypt.byte_at(boxes[b - 1], b - 1 - a) & 0x80u) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); }
+                else { live = true; rs.open(boxes, a, b, len, tiles[wave]); }
             }
         }
-        sink.base = nb;
+    }
+    WindowSink sink{lo32, hi32, 0, acc_lo, acc_hi};
+    __syncthreads();
+    for (;;) {
+        if (live) {
+            rs.next_group(sink);
+            if (rs.done()) { rs.close(status); live = false; }
+        }
+        if (lead) cols[wave] = live ? rs.col : len;               // a finished row no longer holds the window
         __syncthreads();
-        if (nb >= len) break;                                     // all 16 rows are through
+        if (window_flush<kCombWaves>(lo32, hi32, sink, cols, len)) break;
     }
 }
 
@@ -838,6 +972,27 @@ hipError_t launch_varint_stream_combine(const uint8_t* d_bytes, size_t n_bytes, 
     else
         varint_stream_combine_kernel<8><<<dim3((unsigned)(groups * jobs)), dim3(8 * 64), 0, s>>>(
             d_bytes, n_bytes, d_offsets, rows_per_job, groups, len, d_acc_lo, d_acc_hi, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_sealed_stream_combine(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
+                                        size_t max_box_bytes, const SboxState* d_states, size_t len, uint64_t* d_acc_lo,
+                                        int64_t* d_acc_hi, uint32_t* d_status, hipStream_t s, int* waves) {
+    if (waves) *waves = 0;
+    if (rows == 0) return hipSuccess;
+    // 8 rows per workgroup (75 KB of LDS: two workgroups per CU).  The 16-row instance needs 117 KB - ONE workgroup per CU, so
+    // the plaintext kernel's reason for going wide does not carry over - and measured 12.99 ms against 8.47 ms on 2000 boxes
+    // (profiles/r07/clerk_job_fused.txt); no larger job has been timed, so it is reachable through the A/B knob only
+    const bool wide = knob(KNOB_SEALED_WAVES) == 16;
+    const uint64_t groups = vceil(rows, wide ? 16 : 8);
+    if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (waves) *waves = wide ? 16 : 8;
+    if (wide)
+        sealed_stream_combine_kernel<16><<<dim3((unsigned)groups), dim3(16 * 64), 0, s>>>(d_boxes, slot, d_row_bytes, max_box_bytes, d_states,
+                                                                                       rows, len, d_acc_lo, d_acc_hi, d_status);
+    else
+        sealed_stream_combine_kernel<8><<<dim3((unsigned)groups), dim3(8 * 64), 0, s>>>(d_boxes, slot, d_row_bytes, max_box_bytes, d_states,
+                                                                                     rows, len, d_acc_lo, d_acc_hi, d_status);
     return hipGetLastError();
 }
 
