@@ -613,6 +613,24 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   word (1 over-long value, 2 wrong count, 4 unterminated).  THE REFERENCE FAILS THE WHOLE JOB on one bad
  *                   box ("Sodium decryption failure", sodium.rs:78-80): check *d_status before using finish_dev's output.
  *                   Uses the sealed-box handle's scratch: the one-stream-at-a-time rule above holds for this call too.
+ *
+ *   sda_sealedbox_seal_share_rows_dev : participate.rs:82-101 without the wire buffer - the participant-side counterpart of the
+ *                   call above, and what a shim's ShareEncryptor::encrypt for a batch maps to.  Row r of d_values
+ *                   ([rows][len] int64, row r at d_values + r * row_stride) is zig-zag varint encoded and sealed to
+ *                   pks[(r / rows_per_key) % n_pks] into d_boxes + r * slot_bytes; d_row_bytes[r] = payload bytes + 48.  Box and
+ *                   length are byte for byte what sda_varint_encode_rows_dev followed by sda_sealedbox_seal_rows_dev write for
+ *                   the same ephemeral secret (esk as for seal_rows_dev: NULL = OS entropy, else rows * 32 bytes, TESTS ONLY).
+ *                   The setup pass writes the epk and the per-row key state, ONE kernel then encodes a row and xors the XSalsa20
+ *                   keystream into its bytes while they are in registers and LDS - plaintext varints never reach HBM, there is
+ *                   no wire buffer and no second copy of the tile - and the Poly1305 pass over the ciphertext stores the tags.
+ *                   A recipient key of small order is refused per row exactly as by seal_rows_dev: d_row_bytes[r] = 0, the epk is
+ *                   written, nothing is encoded or encrypted, no tag is stored.  Nothing is written past byte d_row_bytes[r] of a
+ *                   live row's slot or past byte 32 of a refused one.  len == 0 gives the 48-byte box of the empty message;
+ *                   rows == 0 returns SDA_OK.  SDA_ERR_INVALID_ARGUMENT before any launch for: a NULL handle or pointer
+ *                   (d_values may be NULL only when len == 0), row_stride < len, slot_bytes not a multiple of 16 or below
+ *                   sda_varint_slot_size(len) + 48, d_boxes not 16-byte aligned, n_pks == 0 or rows_per_key == 0, the box
+ *                   handle and the codec on different devices.  Ephemeral secrets are uploaded, used and wiped as in
+ *                   seal_rows_dev.  Uses the sealed-box handle's scratch: the one-stream-at-a-time rule holds.
  * ============================================================================================= */
 #define SDA_SEALBYTES 48
 typedef struct sda_sealedbox sda_sealedbox_t;
@@ -632,6 +650,10 @@ int  sda_sealedbox_seal(sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t*
                         const uint8_t* msg, size_t len, uint8_t* out, size_t out_cap);
 int  sda_sealedbox_open(sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* box, size_t len,
                         uint8_t* out, size_t out_cap, size_t* out_len);
+int  sda_sealedbox_seal_share_rows_dev(sda_sealedbox_t* b, sda_varint_codec_t* codec, const uint8_t* pks, size_t n_pks,
+                                       size_t rows_per_key, const uint8_t* esk /* NULL = OS entropy; else rows*32, tests only */,
+                                       const int64_t* d_values, size_t rows, size_t len, size_t row_stride, uint8_t* d_boxes,
+                                       size_t slot_bytes, uint64_t* d_row_bytes, void* stream);
 int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
                                                const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,

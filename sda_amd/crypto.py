@@ -699,6 +699,16 @@ class SealedBox(_Handle):
         check(self._lib.sda_sealedbox_seal_rows_dev(self._h, allpk, len(pks), rows_per_key, esk, d_msgs, msg_slot, d_msg_bytes, rows,
                                                     max_msg_bytes, d_boxes, slot_bytes, d_row_bytes, stream or None))
 
+    def seal_share_rows_dev(self, codec: "VarintCodec", pks: Sequence[bytes], rows_per_key: int, d_values: int, rows: int,
+                            length: int, row_stride: int, d_boxes: int, slot_bytes: int, d_row_bytes: int,
+                            esk: Optional[bytes] = None, stream: int = 0) -> None:
+        """share rows [rows][length] -> sealed boxes in one call (participate.rs:82-101): varint encode and XSalsa20 in one
+        pass, no wire buffer.  Box r at d_boxes + r*slot_bytes, d_row_bytes[r] = payload bytes + 48 (0: the row was refused)"""
+        allpk = b"".join(pks)
+        assert len(allpk) == 32 * len(pks) and (esk is None or len(esk) == 32 * rows)
+        check(self._lib.sda_sealedbox_seal_share_rows_dev(self._h, codec._h, allpk, len(pks), rows_per_key, esk, d_values or None, rows,
+                                                          length, row_stride, d_boxes, slot_bytes, d_row_bytes, stream or None))
+
 
 class ShareEncryptor:
     """encryption/sodium.rs:33-46: zig-zag varint encode every share, then seal the bytes for the clerk's key."""
@@ -708,6 +718,27 @@ class ShareEncryptor:
 
     def encrypt(self, shares, esk: Optional[bytes] = None) -> bytes:
         return self._box.seal(self._codec.encode(shares), self.pk, esk)
+
+    def encrypt_rows(self, shares_2d, esk: Optional[bytes] = None) -> List[bytes]:
+        """`encrypt` for a batch of share vectors (one per row) through ONE call of sda_sealedbox_seal_share_rows_dev: the
+        counterpart of ShareCombiner.combine_sealed_job.  esk injects rows*32 bytes of ephemeral secrets (tests only)."""
+        from .device import DeviceBuffer, DeviceBytes
+        m = np.ascontiguousarray(shares_2d, dtype=np.int64)
+        if m.ndim != 2:
+            raise ValueError("encrypt_rows takes a matrix: one share vector per row")
+        rows, length = m.shape
+        if rows == 0:
+            return []
+        d_values = DeviceBuffer.from_numpy(m) if length else None
+        slot = self._codec.slot_size(length) + SealedBox.SEALBYTES
+        d_boxes, d_lens = DeviceBytes(rows * slot), DeviceBytes(rows * 8).zero()
+        self._box.seal_share_rows_dev(self._codec, [self.pk], rows, d_values.ptr if length else 0, rows, length, length,
+                                      d_boxes.ptr, slot, d_lens.ptr, esk)
+        lens = np.frombuffer(d_lens.to_bytes(), dtype="<u8")
+        if (lens == 0).any():
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "sealing refused: the recipient public key is a small-order point (all-zero shared secret)")
+        raw = d_boxes.to_bytes()
+        return [bytes(raw[r * slot:r * slot + int(lens[r])]) for r in range(rows)]
 
 
 class ShareDecryptor:

@@ -13,6 +13,11 @@ struct sda_sealedbox;
 int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot_bytes,
                                const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status,
                                int device, hipStream_t s, const sda::SboxState** d_states);
+// sda_sealedbox_seal_share_rows_dev after its argument checks (sda_sealedbox.cpp): stage the keys, setup, encode + encrypt in one
+// pass (launch_varint_seal_stream), authenticate, wipe the ephemeral secrets - all on the handle's scratch
+int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key, const uint8_t* esk,
+                                   const sda::VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
+int capi_sealedbox_device(const sda_sealedbox* b);
 
 // ---- path-selection knobs (A/B measurements and parity tests of the non-default kernels) -----------------------------------
 // A release build of the library reads NO environment variable: a knob changes only through the test-only entry point

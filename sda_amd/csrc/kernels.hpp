@@ -323,6 +323,11 @@ struct SboxState;
 hipError_t launch_sealed_stream_combine(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
                                         size_t max_box_bytes, const SboxState* d_states, size_t len, uint64_t* d_acc_lo,
                                         int64_t* d_acc_hi, uint32_t* d_status, hipStream_t s, int* waves);
+// share rows -> the ciphertext of their sealed boxes in one pass (varint encode + XSalsa20 keystream, no wire buffer): row r to
+// d_boxes + r * slot_bytes + 48 under d_states[r] (written by launch_sealedbox_seal_setup), its message length to d_msg_bytes[r];
+// a row whose state says `bad` is left alone (length 0)
+hipError_t launch_varint_seal_stream(const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                     uint64_t* d_msg_bytes, hipStream_t s);
 hipError_t launch_varint_rowcheck(const uint8_t* d_bytes, size_t n_bytes, const uint64_t* d_offsets, size_t rows,
                                   size_t len, const uint64_t* d_block_val_off, uint32_t* d_status, hipStream_t s);
 
@@ -363,6 +368,13 @@ hipError_t launch_sealedbox_seal(const uint8_t* d_esk, const uint8_t* d_pks, siz
                                  const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes, size_t rows,
                                  size_t max_msg_bytes, uint8_t* d_boxes, size_t slot, uint64_t* d_row_bytes, SboxState* d_states,
                                  uint32_t* d_partial, hipStream_t s);
+// the halves of launch_sealedbox_seal either side of its keystream pass, for a caller that writes the ciphertext itself
+// (launch_varint_seal_stream): setup = ladders, epk and per-row state; auth = Poly1305 over the ciphertext in the boxes
+// (d_msg_bytes[r] message bytes at box offset 48), tag, d_row_bytes[r] = message bytes + 48 (0 for a refused row)
+hipError_t launch_sealedbox_seal_setup(const uint8_t* d_esk, const uint8_t* d_pks, size_t n_pks, size_t rows_per_key, uint8_t* d_boxes,
+                                       size_t slot, size_t rows, SboxState* d_states, hipStream_t s);
+hipError_t launch_sealedbox_seal_auth(const uint64_t* d_msg_bytes, size_t rows, size_t max_msg_bytes, uint8_t* d_boxes, size_t slot,
+                                      uint64_t* d_row_bytes, SboxState* d_states, uint32_t* d_partial, hipStream_t s);
 // test only (sda_debug_poly1305_rows_dev): Poly1305 of message r (d_msgs + r * msg_slot, 16-byte aligned) under the one-time key
 // d_keys[32 r .. 32 r + 32) through the production poly / final kernels; tag at d_heads + 48 r + 32, d_head_bytes[r] = length + 48
 hipError_t launch_sealedbox_poly_test(const uint8_t* d_keys, const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes,

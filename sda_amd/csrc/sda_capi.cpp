@@ -2498,6 +2498,29 @@ extern "C" int sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c
     return c->mark_pending(s);
 }
 
+// a participation's share rows straight into sealed boxes (participate.rs:82-101): setup, ONE pass that encodes and encrypts, tags
+extern "C" int sda_sealedbox_seal_share_rows_dev(sda_sealedbox_t* b, sda_varint_codec_t* codec, const uint8_t* pks, size_t n_pks,
+                                                 size_t rows_per_key, const uint8_t* esk, const int64_t* d_values, size_t rows,
+                                                 size_t len, size_t row_stride, uint8_t* d_boxes, size_t slot_bytes,
+                                                 uint64_t* d_row_bytes, void* stream) {
+    if (!b || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pks || n_pks == 0 || rows_per_key == 0) return fail(SDA_ERR_INVALID_ARGUMENT, "bad recipient key arguments");
+    if (!d_boxes || !d_row_bytes || (len > 0 && !d_values)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (row_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < len");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    if (len > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(len) + SDA_SEALBYTES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(len) + 48");
+    if (capi_sealedbox_device(b) != codec->ctx.device)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the sealed-box handle lives on device %d, the codec on device %d", capi_sealedbox_device(b), codec->ctx.device);
+    if (rows == 0) return SDA_OK;
+    SDA_TRY(codec->ctx.use());
+    SDA_TRY(capi_sealedbox_seal_share_rows(b, pks, n_pks, rows_per_key, esk, VarintRows{d_values, rows, len, row_stride}, d_boxes, slot_bytes,
+                                           d_row_bytes, codec->ctx.pick(stream)));
+    note_kernel("varint_seal_stream_kernel + sbox_poly_kernel");                    // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return SDA_OK;
+}
+
 extern "C" int sda_share_combiner_update_varint(sda_share_combiner_t* c, sda_varint_codec_t* codec, const uint8_t* bytes,
                                                 size_t n_bytes) {
     if (!c || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");

@@ -22,7 +22,7 @@ struct sda_sealedbox {
     void* d_partial = nullptr; size_t partial_cap = 0;     // Poly1305 partial sums
     void* d_keys = nullptr; size_t keys_cap = 0;           // ephemeral secrets + recipient keys (seal)
     void* d_io = nullptr; size_t io_cap = 0;               // host-form staging
-    void* d_lens = nullptr; size_t lens_cap = 0;           // message lengths of a verify-only pass (nobody reads them)
+    void* d_lens = nullptr; size_t lens_cap = 0;           // message lengths: of a verify-only pass (nobody reads them), of a fused seal
 };
 
 namespace {
@@ -53,6 +53,28 @@ int entropy(void* buf, size_t len) {
     return SDA_OK;
 }
 bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// ephemeral secrets (esk, or OS entropy when NULL) and recipient keys into the handle's key scratch; returns once the host copies
+// of the secrets are no longer needed.  The caller wipes d_esk on the stream after its last use: the secrets are single-use.
+int stage_keys(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, const uint8_t* esk, size_t rows, hipStream_t s, uint8_t** d_esk_out,
+               uint8_t** d_pks_out) {
+    const size_t key_bytes = rows * 32 + n_pks * 32;
+    if (int st = reserve(b->d_keys, b->keys_cap, key_bytes, true)) return st;
+    uint8_t* d_esk = static_cast<uint8_t*>(b->d_keys);
+    uint8_t* d_pks = d_esk + rows * 32;
+    std::vector<uint8_t> fresh;
+    if (!esk) {                                             // crypto_box_seal: a fresh key pair per box (OS entropy)
+        fresh.resize(rows * 32);
+        if (int st = entropy(fresh.data(), fresh.size())) return st;
+        esk = fresh.data();
+    }
+    hipError_t e = hipMemcpyAsync(d_esk, esk, rows * 32, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pks, pks, n_pks * 32, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);       // the host copies of the secrets can go now
+    if (!fresh.empty()) explicit_bzero(fresh.data(), fresh.size());
+    if (e != hipSuccess) return capi_fail(SDA_ERR_HIP, "uploading the keys failed: %s", hipGetErrorString(e));
+    *d_esk_out = d_esk; *d_pks_out = d_pks;
+    return SDA_OK;
+}
 }  // namespace
 
 extern "C" int sda_sealedbox_new(sda_sealedbox_t** out) {
@@ -123,27 +145,37 @@ extern "C" int sda_sealedbox_seal_rows_dev(sda_sealedbox_t* b, const uint8_t* pk
     if (msg_slot < max_msg_bytes) return capi_fail(SDA_ERR_INVALID_ARGUMENT, "msg_slot < max_msg_bytes");
     if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
     if (int st = scratch(b, rows, max_msg_bytes)) return st;
-    const size_t key_bytes = rows * 32 + n_pks * 32;
-    if (int st = reserve(b->d_keys, b->keys_cap, key_bytes, true)) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    uint8_t* d_esk = static_cast<uint8_t*>(b->d_keys);
-    uint8_t* d_pks = d_esk + rows * 32;
-    std::vector<uint8_t> fresh;
-    if (!esk) {                                             // crypto_box_seal: a fresh key pair per box (OS entropy)
-        fresh.resize(rows * 32);
-        if (int st = entropy(fresh.data(), fresh.size())) return st;
-        esk = fresh.data();
-    }
-    hipError_t e = hipMemcpyAsync(d_esk, esk, rows * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pks, pks, n_pks * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);       // the host copies of the secrets can go now
-    if (!fresh.empty()) explicit_bzero(fresh.data(), fresh.size());
-    if (e != hipSuccess) return capi_fail(SDA_ERR_HIP, "uploading the keys failed: %s", hipGetErrorString(e));
-    e = launch_sealedbox_seal(d_esk, d_pks, n_pks, rows_per_key, d_msgs, msg_slot, d_msg_bytes, rows, max_msg_bytes, d_boxes,
-                              slot_bytes, d_row_bytes, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
+    uint8_t *d_esk = nullptr, *d_pks = nullptr;
+    if (int st = stage_keys(b, pks, n_pks, esk, rows, s, &d_esk, &d_pks)) return st;
+    hipError_t e = launch_sealedbox_seal(d_esk, d_pks, n_pks, rows_per_key, d_msgs, msg_slot, d_msg_bytes, rows, max_msg_bytes, d_boxes,
+                                         slot_bytes, d_row_bytes, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
     if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box seal launch failed: %s", hipGetErrorString(e));
 }
+
+// for sda_sealedbox_seal_share_rows_dev (sda_capi.cpp), which has checked the arguments: setup, then ONE pass that encodes the rows
+// and encrypts them into the boxes, then the Poly1305 pass and the tags.  The message lengths the encode pass finds go through the
+// handle's d_lens; key staging and wiping as in seal_rows_dev.
+int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key, const uint8_t* esk,
+                                   const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
+    const size_t rows = R.rows, max_msg = R.len * 10;      // a share is at most 10 bytes on the wire
+    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
+    if (int st = scratch(b, rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
+    uint8_t *d_esk = nullptr, *d_pks = nullptr;
+    if (int st = stage_keys(b, pks, n_pks, esk, rows, s, &d_esk, &d_pks)) return st;
+    SboxState* d_states = static_cast<SboxState*>(b->d_states);
+    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
+    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, n_pks, rows_per_key, d_boxes, slot_bytes, rows, d_states, s);
+    if (e == hipSuccess) e = launch_varint_seal_stream(R, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    if (e == hipSuccess)
+        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing share rows: launch failed: %s", hipGetErrorString(e));
+}
+
+int capi_sealedbox_device(const sda_sealedbox* b) { return b->device; }
 
 // ---- host forms: one payload, staged through the device (what ShareEncryptor::encrypt / ShareDecryptor::decrypt call) ----
 extern "C" int sda_sealedbox_seal(sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t* esk, const uint8_t* msg, size_t len,

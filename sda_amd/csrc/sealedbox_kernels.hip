@@ -426,21 +426,43 @@ hipError_t launch_sealedbox_open(const uint8_t pk[32], const uint8_t sk[32], con
                 kPassStream, 0, s);
 }
 
+// The two halves of a seal either side of the pass that writes the ciphertext.  Setup: both X25519 ladders, the epk into the
+// box, the per-row state.  Authenticate: Poly1305 over the ciphertext in the boxes (d_msg_bytes[r] message bytes), tag and length.
+hipError_t launch_sealedbox_seal_setup(const uint8_t* d_esk, const uint8_t* d_pks, size_t n_pks, size_t rows_per_key, uint8_t* d_boxes,
+                                       size_t slot, size_t rows, SboxState* d_states, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    sbox_setup_seal_kernel<<<dim3((unsigned)cdiv64(8 * rows, 64)), dim3(64), 0, s>>>(d_esk, d_pks, n_pks, rows_per_key, d_boxes, slot, rows,
+                                                                                d_states);
+    return hipGetLastError();
+}
+
+static hipError_t seal_final(const uint64_t* d_msg_bytes, size_t rows, size_t max_msg_bytes, uint8_t* d_boxes, size_t slot,
+                             uint64_t* d_row_bytes, SboxState* d_states, uint32_t* d_partial, hipStream_t s) {
+    sbox_final_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_partial, sbox_regions(max_msg_bytes), d_states, d_boxes, slot,
+                                                                           d_msg_bytes, 0, max_msg_bytes, rows, 1, d_row_bytes, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_sealedbox_seal_auth(const uint64_t* d_msg_bytes, size_t rows, size_t max_msg_bytes, uint8_t* d_boxes, size_t slot,
+                                      uint64_t* d_row_bytes, SboxState* d_states, uint32_t* d_partial, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    if (hipError_t e = bulk(nullptr, 0, 0, nullptr, 0, 0, d_boxes, slot, 48, d_msg_bytes, 0, rows, max_msg_bytes, d_states, d_partial,
+                            kPassPoly, 0, s))
+        return e;
+    return seal_final(d_msg_bytes, rows, max_msg_bytes, d_boxes, slot, d_row_bytes, d_states, d_partial, s);
+}
+
 hipError_t launch_sealedbox_seal(const uint8_t* d_esk, const uint8_t* d_pks, size_t n_pks, size_t rows_per_key,
                                  const uint8_t* d_msgs, size_t msg_slot, const uint64_t* d_msg_bytes, size_t rows,
                                  size_t max_msg_bytes, uint8_t* d_boxes, size_t slot, uint64_t* d_row_bytes, SboxState* d_states,
                                  uint32_t* d_partial, hipStream_t s) {
     if (rows == 0) return hipSuccess;
-    sbox_setup_seal_kernel<<<dim3((unsigned)cdiv64(8 * rows, 64)), dim3(64), 0, s>>>(d_esk, d_pks, n_pks, rows_per_key, d_boxes, slot, rows,
-                                                                                d_states);
-    if (hipError_t e = hipGetLastError()) return e;
-    // encrypt into the box, then authenticate the ciphertext
+    if (hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, n_pks, rows_per_key, d_boxes, slot, rows, d_states, s)) return e;
+    // encrypt into the box, then authenticate the ciphertext (per 65535 rows: keystream pass, Poly1305 pass), then the tags
     if (hipError_t e = bulk(d_msgs, msg_slot, 0, d_boxes, slot, 48, d_boxes, slot, 48, d_msg_bytes, 0, rows, max_msg_bytes, d_states,
                             d_partial, kPassStream, kPassPoly, s))
         return e;
-    sbox_final_kernel<<<dim3((unsigned)cdiv64(rows, 64)), dim3(64), 0, s>>>(d_partial, sbox_regions(max_msg_bytes), d_states, d_boxes, slot,
-                                                                           d_msg_bytes, 0, max_msg_bytes, rows, 1, d_row_bytes, nullptr, nullptr);
-    return hipGetLastError();
+    return seal_final(d_msg_bytes, rows, max_msg_bytes, d_boxes, slot, d_row_bytes, d_states, d_partial, s);
 }
 
 // ---- test only (include/sda_hip_debug.h: sda_debug_poly1305_rows_dev; not reachable from the release library) --------

@@ -624,17 +624,26 @@ __device__ __forceinline__ void enc_load2(const int64_t* __restrict__ src, uint6
     }
 }
 
-__global__ __launch_bounds__(kStreamWaves * 64) void varint_stream_encode_kernel(VarintRows R, uint8_t* __restrict__ out,
-                                                                                 uint64_t slot,
-                                                                                 uint64_t* __restrict__ row_bytes) {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[kStreamWaves][kEncTile];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t r = (uint64_t)blockIdx.x * kStreamWaves + wave;
-    if (r >= R.rows) return;
+// What the encode loop does to a 16-byte unit between the LDS tile and the global store.  Unit u of a row is its bytes
+// [16 u, 16 u + 16).  The rows of the plaintext kernel leave as they are:
+struct EncPlain {
+    __device__ __forceinline__ bool ends_before(uint64_t) const { return false; }
+    __device__ __forceinline__ bool holds(uint64_t) const { return true; }
+    __device__ __forceinline__ void refill() {}
+    __device__ __forceinline__ void apply(uint4&, uint64_t) const {}
+};
+
+// One wave encodes row r of R to dst (16-byte aligned) and stores its byte count in row_bytes[r].  Crypt: EncPlain, or the
+// XSalsa20 keystream of the row's sealed box (EncXSalsa below), xor-ed into every unit on its way from the tile to global
+// memory.  The write cursor depends on the data (a step emits 8..81 units), so the keystream follows the cursor: a step whose
+// units reach past what the keystream tile holds stores the units it still covers, refills, and stores the rest.
+template <class Crypt>
+__device__ __forceinline__ void encode_row(const VarintRows& R, uint64_t r, uint8_t* __restrict__ dst, uint8_t* tile,
+                                           uint64_t* __restrict__ row_bytes, Crypt& crypt) {
+    const int lane = threadIdx.x & 63;
     const int64_t* __restrict__ src = R.values + r * R.row_stride;
-    uint8_t* __restrict__ dst = out + r * slot;
-    uint32_t* tile32 = reinterpret_cast<uint32_t*>(tiles[wave]);
-    uint4* tile128 = reinterpret_cast<uint4*>(tiles[wave]);
+    uint32_t* tile32 = reinterpret_cast<uint32_t*>(tile);
+    uint4* tile128 = reinterpret_cast<uint4*>(tile);
     const bool vec = (((uintptr_t)src) & 15u) == 0;
     const uint64_t n_steps = (R.len + kEncVals - 1) / kEncVals;
     const uint64_t len = R.len;
@@ -676,8 +685,15 @@ __global__ __launch_bounds__(kStreamWaves * 64) void varint_stream_encode_kernel
             __builtin_amdgcn_wave_barrier();
             const uint32_t have = cb + T, units = have >> 4;              // <= 81 units
             uint4* g = reinterpret_cast<uint4*>(dst + cur);
-            if ((uint32_t)lane < units) g[lane] = tile128[lane];
-            if ((uint32_t)lane + 64 < units) g[lane + 64] = tile128[lane + 64];
+            bool s0 = (uint32_t)lane < units, s1 = (uint32_t)lane + 64 < units;
+            const uint64_t u0 = (cur >> 4) + (uint32_t)lane;              // this lane's units: u0 and u0 + 64
+            if (crypt.ends_before((cur >> 4) + units)) {                  // wave-uniform: the step straddles a refill
+                if (s0 && crypt.holds(u0)) { uint4 v = tile128[lane]; crypt.apply(v, u0); g[lane] = v; s0 = false; }
+                if (s1 && crypt.holds(u0 + 64)) { uint4 v = tile128[lane + 64]; crypt.apply(v, u0 + 64); g[lane + 64] = v; s1 = false; }
+                crypt.refill();
+            }
+            if (s0) { uint4 v = tile128[lane]; crypt.apply(v, u0); g[lane] = v; }
+            if (s1) { uint4 v = tile128[lane + 64]; crypt.apply(v, u0 + 64); g[lane + 64] = v; }
             const uint4 next = tile128[units];                            // bytes past `have` are zero
             carry = make_uint4(__builtin_amdgcn_readfirstlane(next.x), __builtin_amdgcn_readfirstlane(next.y),
                                __builtin_amdgcn_readfirstlane(next.z), __builtin_amdgcn_readfirstlane(next.w));
@@ -687,13 +703,28 @@ __global__ __launch_bounds__(kStreamWaves * 64) void varint_stream_encode_kernel
             cb = have & 15u;
         }
     }
-    // the last bytes of the row
+    // the last bytes of the row: a partial unit of its own
+    if (cb) {
+        if (crypt.ends_before((cur >> 4) + 1)) crypt.refill();
+        crypt.apply(carry, cur >> 4);
+    }
     if ((uint32_t)lane < cb) {
         const uint32_t wsel = lane >> 2;
         const uint32_t word = wsel == 0 ? carry.x : wsel == 1 ? carry.y : wsel == 2 ? carry.z : carry.w;
         dst[cur + lane] = (uint8_t)(word >> (8 * (lane & 3)));
     }
     if (lane == 0) row_bytes[r] = cur + cb;
+}
+
+__global__ __launch_bounds__(kStreamWaves * 64) void varint_stream_encode_kernel(VarintRows R, uint8_t* __restrict__ out,
+                                                                                 uint64_t slot,
+                                                                                 uint64_t* __restrict__ row_bytes) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kStreamWaves][kEncTile];
+    const int wave = threadIdx.x >> 6;
+    const uint64_t r = (uint64_t)blockIdx.x * kStreamWaves + wave;
+    if (r >= R.rows) return;
+    EncPlain crypt;
+    encode_row(R, r, out + r * slot, tiles[wave], row_bytes, crypt);
 }
 
 // ---- wire format -> clerk sums without the decoded tile ---------------------------------
@@ -890,6 +921,65 @@ __global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_combine_kernel(
     }
 }
 
+// ---- share rows -> sealed boxes without the wire buffer (participate.rs:82-101: encode_var every share, then seal) --------
+// The encode kernel with the XSalsa20 keystream of the row's box xor-ed into every unit before it is stored: row r goes to
+// boxes + r * slot + 48, where the ciphertext starts 16-byte aligned; plaintext varint bytes exist in registers and LDS only.
+// The setup pass has written the box's epk and the per-row state; the Poly1305 pass over the ciphertext follows (its pieces
+// are indexed from the END of the message, which is only known once the row is through).
+//
+// Geometry as above: unit u of the message is stream piece u + 2, Salsa20 block (u + 2) >> 2.  The wave keeps the 64 blocks
+// base .. base + 63 in its keystream tile ([word][slot], slot stride 66 as XSalsaBytes); all 64 lanes refill it at once
+// (block = base + lane) when the write cursor reaches its end - first at message byte 4064, then every 4096 bytes.
+struct EncXSalsa {
+    uint32_t key[8], n0, n1;                               // wave-uniform: the box's XSalsa20 subkey and nonce tail
+    uint32_t* ks;
+    uint64_t base;                                         // first block of the tile, a multiple of 64
+    __device__ __forceinline__ void fill() {
+        const int lane = threadIdx.x & 63;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the reads of the blocks being replaced are done
+        __builtin_amdgcn_wave_barrier();
+        uint32_t b[16];
+        sbx::salsa20_block(b, key, n0, n1, base + (uint64_t)lane);
+#pragma unroll
+        for (int w = 0; w < 16; ++w) ks[w * kKsStride + lane] = b[w];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void open(const SboxState& st, uint32_t* tile) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) key[i] = st.subkey[i];
+        n0 = st.n0; n1 = st.n1;
+        ks = tile;
+        base = 0;                                          // pieces 0 and 1 (the Poly1305 key) are computed and never read
+        fill();
+    }
+    // units [.., unit_end) reach past the tile / unit u lies inside it (units only ever move forward)
+    __device__ __forceinline__ bool ends_before(uint64_t unit_end) const { return unit_end + 2 > 4 * (base + 64); }
+    __device__ __forceinline__ bool holds(uint64_t u) const { return u + 2 < 4 * (base + 64); }
+    __device__ __forceinline__ void refill() { base += 64; fill(); }
+    __device__ __forceinline__ void apply(uint4& v, uint64_t u) const {
+        const uint32_t p = (uint32_t)(u + 2 - 4 * base);           // piece inside the tile, 0..255
+        const uint32_t* k = ks + (p & 3u) * 4u * kKsStride + (p >> 2);
+        v.x ^= k[0]; v.y ^= k[kKsStride]; v.z ^= k[2 * kKsStride]; v.w ^= k[3 * kKsStride];
+    }
+};
+
+__global__ __launch_bounds__(kStreamWaves * 64) void varint_seal_stream_kernel(VarintRows R, uint8_t* __restrict__ boxes, uint64_t slot,
+                                                                               const SboxState* __restrict__ states,
+                                                                               uint64_t* __restrict__ msg_bytes) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kStreamWaves][kEncTile];
+    __shared__ uint32_t kstream[kStreamWaves][kKsTile];
+    const int wave = threadIdx.x >> 6;
+    const uint64_t r = (uint64_t)blockIdx.x * kStreamWaves + wave;
+    if (r >= R.rows) return;
+    // a row whose recipient key gave the all-zero shared secret is refused: nothing encoded, nothing encrypted under the
+    // degenerate key; the final pass gives it length 0 and no tag
+    if (states[r].bad) { if ((threadIdx.x & 63) == 0) msg_bytes[r] = 0; return; }
+    EncXSalsa crypt;
+    crypt.open(states[r], kstream[wave]);
+    encode_row(R, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 static inline uint64_t vceil(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
@@ -955,6 +1045,15 @@ hipError_t launch_varint_stream_encode(const VarintRows& R, uint8_t* d_out, size
     if (R.rows == 0) return hipSuccess;
     varint_stream_encode_kernel<<<dim3((unsigned)vceil(R.rows, kStreamWaves)), dim3(kStreamWaves * 64), residency_pad_bytes(knob(KNOB_WIRE_WG_PER_CU), 8192), s>>>(
         R, d_out, slot_bytes, d_row_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_varint_seal_stream(const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                     uint64_t* d_msg_bytes, hipStream_t s) {
+    if (R.rows == 0) return hipSuccess;
+    const uint64_t groups = vceil(R.rows, kStreamWaves);
+    if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    varint_seal_stream_kernel<<<dim3((unsigned)groups), dim3(kStreamWaves * 64), 0, s>>>(R, d_boxes, slot_bytes, d_states, d_msg_bytes);
     return hipGetLastError();
 }
 

@@ -209,6 +209,39 @@ struct ShareEncryptor {
     EncryptionKey pk; SealedBox box; ShareCodec codec;
     explicit ShareEncryptor(EncryptionKey k) : pk(std::move(k)) {}
     Encryption encrypt(const std::vector<Share>& shares) { return box.seal(codec.encode(shares), pk); }
+    /// `encrypt` for a batch of share vectors of one length through ONE call (sda_sealedbox_seal_share_rows_dev): no wire
+    /// buffer on the device.  esk: null, or rows * 32 injected ephemeral secrets (tests only).
+    std::vector<Encryption> encrypt_rows(const std::vector<std::vector<Share>>& rows, const uint8_t* esk = nullptr) {
+        std::vector<Encryption> out;
+        if (rows.empty()) return out;
+        const size_t n = rows.size(), len = rows[0].size(), slot = sda_varint_slot_size(len) + SDA_SEALBYTES;
+        std::vector<Share> flat;
+        flat.reserve(n * len);
+        for (const auto& r : rows) {
+            if (r.size() != len) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "encrypt_rows: share vectors of one length");
+            flat.insert(flat.end(), r.begin(), r.end());
+        }
+        struct Dev {                                                // freed on every way out
+            void* p = nullptr;
+            ~Dev() { if (p) sda_dev_free(p); }
+        } d_values, d_boxes, d_lens;
+        detail::check(sda_dev_malloc(&d_values.p, flat.size() * sizeof(Share) + 16));
+        detail::check(sda_dev_malloc(&d_boxes.p, n * slot));
+        detail::check(sda_dev_malloc(&d_lens.p, n * sizeof(uint64_t)));
+        if (!flat.empty()) detail::check(sda_dev_upload(d_values.p, flat.data(), flat.size() * sizeof(Share)));
+        detail::check(sda_sealedbox_seal_share_rows_dev(box.h, codec.h, pk.data(), 1, n, esk, static_cast<const int64_t*>(d_values.p), n, len,
+                                                        len, static_cast<uint8_t*>(d_boxes.p), slot, static_cast<uint64_t*>(d_lens.p), nullptr));
+        detail::check(sda_dev_synchronize());
+        std::vector<uint64_t> lens(n);
+        detail::check(sda_dev_download(lens.data(), d_lens.p, n * sizeof(uint64_t)));
+        for (size_t r = 0; r < n; ++r) {
+            if (lens[r] == 0) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "sealing refused: the recipient public key is a small-order point");
+            Encryption e(lens[r]);
+            detail::check(sda_dev_download(e.data(), static_cast<const uint8_t*>(d_boxes.p) + r * slot, lens[r]));
+            out.push_back(std::move(e));
+        }
+        return out;
+    }
 };
 struct ShareDecryptor {
     EncryptionKey pk; DecryptionKey sk; SealedBox box; ShareCodec codec;
