@@ -321,6 +321,8 @@ int sda_share_combiner_set_residency(sda_share_combiner_t* c, unsigned max_workg
  * jobs = share_count and dimension = batches.  participants == 0 -> clerk-sum only (last tile);
  * prev_participants == 0 -> generation only (first tile).  Randomness: the on-device CSPRNG, stream ids
  * first_participant + p - identical shares to sda_share_generator_generate_batch_dev.
+ * d_prev is caller memory and may hold ANY i64 rows, not only shares an earlier call wrote: the sums are those
+ * sda_share_combiner_update_dev gives for the same rows.
  * For the limb GEMM shapes (a prime below 2^23, k + t > 16) the clerk sum rides inside the share-generation kernel and a
  * short follow-up launch on the same stream finishes it; the two communicate through scratch memory the GENERATOR owns:
  * consecutive calls on one generator go on ONE stream (or are ordered by the caller), like every other use of a handle. */
