@@ -404,8 +404,9 @@ int sda_secret_masker_mask(sda_secret_masker_t* m,
  * (the "mask" a participant sends is its seed, chacha.rs:48-50; mask_stride >= that many), masked[p][i] =
  * (secrets[p][i] + i-th rand-0.3 ChaChaRng gen_range value of that seed) mod q; len must equal the scheme's dimension
  * (SDA_ERR_ASSERTION, chacha.rs:26); the call synchronises `stream`.  Full masks are combined on the recipient side
- * exactly like shares (full.rs:37-52 == combiner.rs:15-29): feed them to an sda_share_combiner begun with
- * jobs == 1; ChaCha seeds go to sda_mask_combiner_combine. */
+ * exactly like shares (full.rs:37-52 == combiner.rs:15-29).  Either kind of mask stays on the device for the recipient:
+ * d_masks rows (Full mask vectors, ChaCha seeds) go to sda_mask_combiner_update_dev, their sealed boxes to
+ * sda_mask_combiner_update_sealed_rows_dev; sda_mask_combiner_combine is the host form of the same sums. */
 int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const int64_t* d_secrets, size_t participants, size_t len,
                                      size_t secrets_stride, uint64_t first_participant, int64_t* d_masks,
                                      size_t mask_stride, int64_t* d_masked, size_t masked_stride, void* stream);
@@ -423,6 +424,31 @@ void sda_mask_combiner_free(sda_mask_combiner_t* c);
 int sda_mask_combiner_combine(sda_mask_combiner_t* c,
                               const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                               int64_t* out, size_t out_cap, size_t* out_len);
+
+/* combine() as a streaming job on the device - the recipient's step, client/src/receive.rs:101-118, with the masks in
+ * HBM; mirrors sda_share_combiner_begin_dev / update_dev / finish_dev.  Any number of update calls of either form (the
+ * sealed one is declared with the sealed boxes below) may come between begin_dev and finish_dev, freely mixed; rows == 0
+ * is SDA_OK and launches nothing; update / finish before begin -> SDA_ERR_STATE; a NULL handle or pointer ->
+ * SDA_ERR_INVALID_ARGUMENT before anything touches a device.  NO UPDATE CALL SYNCHRONISES THE STREAM OR COPIES ANYTHING
+ * TO THE HOST: everything is enqueued on `stream` (NULL: the handle's), so d_rows / d_boxes may be reused as soon as later
+ * work on the same stream overwrites them.  The handle's scratch (keys, rejection records, repair lists) is shared by its
+ * calls: a mask combiner serves ONE stream at a time, the sealed-box rule.  Scratch that held keys is zeroed by
+ * finish_dev and wiped when the handle is freed.  The value mode is read at begin_dev.
+ *
+ *   begin_dev : ChaCha (chacha.rs:58): dimension must be the scheme's, else SDA_ERR_INVALID_ARGUMENT.  Full
+ *               (full.rs:40-41): the length every mask must have.  None: any dimension, no device.
+ *   update_dev: rows [rows][row_len] int64, row r at d_rows + r * row_stride (row_stride >= row_len).
+ *               ChaCha (chacha.rs:60-73): a row is a seed, words used `as u32` (chacha.rs:62-64), only the first 8 count,
+ *               row_len == 0 is the all-zero key; both value modes give the same numbers.  Full (full.rs:43-49): a row is
+ *               a mask vector, row_len != dimension -> SDA_ERR_ASSERTION (full.rs:43); SDA_VALUES_RUST_SIGNED sums as the
+ *               reference does.  None (none.rs:23): row_len != 0 -> SDA_ERR_ASSERTION.
+ *   finish_dev: d_out[0 .. dimension) = bit for bit what sda_mask_combiner_combine returns for the same rows in the same
+ *               order (ChaCha with no seed at all: `dimension` zeros, chacha.rs:58); out_cap < dimension ->
+ *               SDA_ERR_INVALID_ARGUMENT; None writes nothing.  Ends the job: another begin_dev may follow. */
+int sda_mask_combiner_begin_dev(sda_mask_combiner_t* c, size_t dimension, void* stream);
+int sda_mask_combiner_update_dev(sda_mask_combiner_t* c, const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride,
+                                 void* stream);
+int sda_mask_combiner_finish_dev(sda_mask_combiner_t* c, int64_t* d_out, size_t out_cap, void* stream);
 
 /* new_secret_unmasker(&scheme) - masking/mod.rs:77-94 */
 int  sda_secret_unmasker_new(const sda_masking_scheme_t* scheme, sda_secret_unmasker_t** out);
@@ -633,6 +659,24 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   sda_varint_slot_size(len) + 48, d_boxes not 16-byte aligned, n_pks == 0 or rows_per_key == 0, the box
  *                   handle and the codec on different devices.  Ephemeral secrets are uploaded, used and wiped as in
  *                   seal_rows_dev.  Uses the sealed-box handle's scratch: the one-stream-at-a-time rule holds.
+ *
+ *   sda_mask_combiner_update_sealed_rows_dev : receive.rs:101-118 from the participants' sealed mask encryptions - an update
+ *                   form of the mask combiner's device job (sda_mask_combiner_begin_dev above), rows laid out as for
+ *                   open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does (d_ok[r] when d_ok is given;
+ *                   *d_status |= 16 for a box that does not authenticate, is shorter than 48 or longer than max_box_bytes
+ *                   bytes, or has an all-zero shared secret).  A row that failed adds nothing.  ChaCha (sodium.rs:36-43: the
+ *                   payload is the varint encoding of the seed words; chacha.rs:60-73): step 2 decrypts the small rows that
+ *                   passed in registers and decodes them straight into ChaCha keys in the handle's scratch - a value of more
+ *                   than 10 bytes sets status bit 1, a payload that ends inside a value bit 4, as sda_varint_decode_rows_dev
+ *                   does, and such a row adds nothing either; there is no value-count check (the reference takes a seed of any
+ *                   length: words past the eighth are decoded for validity and ignored, a 48-byte box is the empty seed) -
+ *                   and step 3 expands and sums the keys as update_dev does.  No caller-visible plaintext buffer, no host copy.
+ *                   Full (full.rs:37-52): step 2 is the one-pass decrypt + decode + sum of
+ *                   sda_share_combiner_update_sealed_rows_dev on the handle's own sums, status bits as there;
+ *                   SDA_VALUES_RUST_SIGNED -> SDA_ERR_UNSUPPORTED, as the share combiner's wire-fed updates.  None ->
+ *                   SDA_ERR_UNSUPPORTED.  THE REFERENCE FAILS THE WHOLE AGGREGATION on one bad box (sodium.rs:78-80): check
+ *                   *d_status before using finish_dev's output.  Uses the sealed-box handle's scratch and the combiner's:
+ *                   one stream at a time for both.
  * ============================================================================================= */
 #define SDA_SEALBYTES 48
 typedef struct sda_sealedbox sda_sealedbox_t;
@@ -660,6 +704,11 @@ int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_vari
                                                const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
                                                uint32_t* d_ok /* optional */, uint32_t* d_status, void* stream);
+/* receive.rs:101-118: the participants' sealed mask encryptions summed into the mask combiner's device job (see above) */
+int  sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                              const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
+                                              size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
+                                              uint32_t* d_ok /* optional */, uint32_t* d_status, void* stream);
 
 /* =============================================================================================
  * Cross-GPU modular reduction (new; no reference counterpart - SURVEY.md 8e: the reference's parties meet over HTTP).

@@ -201,6 +201,12 @@ SIGNATURES = {
     "sda_share_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
                                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                             C.c_void_p]),
+    "sda_mask_combiner_begin_dev": (C.c_int, [_H, C.c_size_t, C.c_void_p]),
+    "sda_mask_combiner_update_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "sda_mask_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
+                                                           C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]),
+    "sda_mask_combiner_finish_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sda_comm_unique_id": (C.c_int, [c_u8p]),
     "sda_comm_init": (C.c_int, [c_u8p, C.c_int, C.c_int, _HP]),
     "sda_comm_free": (None, [_H]),

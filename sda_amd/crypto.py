@@ -452,6 +452,59 @@ class MaskCombiner(_Handle):
         _check_mask(self._lib.sda_mask_combiner_combine(self._h, ptrs, lens, len(arrs), _ptr(out), cap, C.byref(n_out)))
         return out[:n_out.value].copy()
 
+    # streaming device form (receive.rs:101-118 with the masks in HBM): no update synchronises or copies to the host
+    def begin_dev(self, dimension: int, stream: int = 0) -> None:
+        check(self._lib.sda_mask_combiner_begin_dev(self._h, dimension, stream or None))
+        self._dimension = dimension
+
+    def update_dev(self, d_rows: int, rows: int, row_len: int, row_stride: int, stream: int = 0) -> None:
+        """rows of masks in HBM: ChaCha seeds (words used `as u32`, the first 8 count) or Full mask vectors"""
+        _check_mask(self._lib.sda_mask_combiner_update_dev(self._h, d_rows or None, rows, row_len, row_stride, stream or None))
+
+    def update_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", pk: bytes, sk: bytes, d_boxes: int,
+                               slot_bytes: int, d_row_bytes: int, rows: int, max_box_bytes: int, d_status: int, d_ok: int = 0,
+                               stream: int = 0) -> None:
+        """the participants' mask encryptions while they are still sealed boxes (the SDAJOBv1 SEALED layout).
+        *d_status & 16: some box failed, the result must not be used (sodium.rs:78-80)"""
+        check(self._lib.sda_mask_combiner_update_sealed_rows_dev(self._h, codec._h if codec else None, box._h if box else None,
+                                                                 pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes,
+                                                                 d_ok or None, d_status, stream or None))
+
+    def finish_dev(self, d_out: int, out_cap: int, stream: int = 0) -> None:
+        check(self._lib.sda_mask_combiner_finish_dev(self._h, d_out or None, out_cap, stream or None))
+
+    def combine_sealed_job(self, blob, pk: bytes, sk: bytes, dimension: Optional[int] = None) -> np.ndarray:
+        """receive.rs:101-118 for an SDAJOBv1 blob of sealed mask encryptions: open every one, combine the masks.  One bad
+        box fails the job ("Sodium decryption failure"), so does a payload that is no varint vector.  ChaCha: the result
+        has the scheme's dimension (chacha.rs:58); Full: `dimension` is the length every mask must have ("Wrong dimension"
+        otherwise)."""
+        from .device import DeviceBuffer, DeviceBytes
+        job = JobContainer.parse(bytes(blob))
+        L = job.layout
+        if L.payload_kind != capi.JOB_SEALED:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "combine_sealed_job needs a job of sealed boxes (payload kind SEALED)")
+        if isinstance(self.scheme, ChaCha):
+            dimension = self.scheme.dimension
+        elif dimension is None:
+            raise ValueError("combine_sealed_job needs the masks' dimension for this scheme")
+        d_out = DeviceBuffer(max(dimension, 1))
+        d_status = DeviceBuffer(1).zero()
+        self.begin_dev(dimension)
+        if L.rows:
+            d_job = DeviceBytes.from_bytes(job.blob)
+            codec, box = VarintCodec(), SealedBox()
+            self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes,
+                                        d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status.ptr)
+        self.finish_dev(d_out.ptr, dimension)
+        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
+        if status & 16:
+            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
+        if status & 2:
+            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")
+        if status:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        return d_out.to_numpy()[:dimension].copy()
+
 
 class SecretUnmasker(_Handle):
     """masking/mod.rs:29-31; impl none.rs:28-33, full.rs:54-67, chacha.rs:79-93."""

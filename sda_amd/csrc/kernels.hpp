@@ -269,6 +269,33 @@ hipError_t launch_chacha_mask_slow(const uint32_t* d_seeds, const uint32_t* d_li
                                    uint64_t* d_acc_lo, int64_t* d_acc_hi, bool subtract_naive,
                                    hipStream_t s);
 
+// ---- the same sums with every decision on the device (sda_mask_combiner_*_dev: no launch below waits for a result) ----
+// seed rows ([rows][row_len] int64, stride row_stride; words `as u32`, the first 8 count) -> 8 key words per row
+hipError_t launch_mask_rows_to_keys(const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride, uint32_t* d_keys,
+                                    hipStream_t s);
+// launch_chacha_mask_accumulate over the first *d_n_seeds (<= max_seeds, which sizes the grid) keys
+hipError_t launch_chacha_mask_accumulate_counted(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
+                                                 const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
+                                                 RejectRecord* d_rejects, hipStream_t s);
+// the repair plan from the fast pass's records: d_plan[0] seeds with 1..3 rejections into d_shift_list, d_plan[1] with more into
+// d_exact_list (both counters zeroed by the caller, both lists hold up to n entries, in no particular order)
+hipError_t launch_chacha_mask_plan(const RejectRecord* d_rejects, size_t n, uint32_t* d_plan, uint32_t* d_shift_list,
+                                   uint32_t* d_exact_list, hipStream_t s);
+// launch_chacha_mask_shift / _slow over a list of *d_n_list (<= max_list) entries: a fixed, bounded grid whose workgroups stride
+// over the entries.  d_list == nullptr (exact order only): keys 0 .. *d_n_list - 1
+hipError_t launch_chacha_mask_shift_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
+                                           const RejectRecord* d_rejects, size_t dimension, uint64_t zone, uint64_t* d_acc_lo,
+                                           int64_t* d_acc_hi, hipStream_t s);
+hipError_t launch_chacha_mask_slow_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
+                                          size_t dimension, const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo,
+                                          int64_t* d_acc_hi, bool subtract_naive, hipStream_t s);
+// sealed seed rows (box r at d_boxes + r * slot, tags checked by launch_sealedbox_verify: rows marked bad in d_states are skipped)
+// -> the keys of the rows that decrypt to a well-formed varint seed, packed from d_keys[0], their number added to *d_n_keys;
+// *d_status |= 1 (a value of more than 10 bytes) / 4 (ends inside a value) for a row that does not
+struct SboxState;
+hipError_t launch_sealed_seed_keys(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
+                                   const SboxState* d_states, uint32_t* d_keys, uint32_t* d_n_keys, uint32_t* d_status, hipStream_t s);
+
 // the same expansion applied to each participant's own vector: out[p][i] = (secrets[p][i] + mask_i(seed p)) mod m
 // (chacha.rs:36-47 for a device-resident tile).  Fast pass for every participant (rejections recorded in d_rejects,
 // zeroed by the caller), then the repair pass for the listed ones: shift list (1..3 rejections), exact-order list

@@ -300,6 +300,11 @@ struct DevBuf {
         cap = want;
         return SDA_OK;
     }
+    // ... for a buffer that holds key material while it grows: the old allocation is zeroed before it is freed
+    int reserve_wiped(size_t bytes) {
+        if (bytes > cap && p) (void)hipMemset(p, 0, cap);
+        return reserve(bytes);
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr; cap = 0;
@@ -1872,6 +1877,8 @@ struct MaskCore {
     DevBuf tile, d_a, d_b, d_out, d_seeds, d_flags, d_list;
     Drbg drbg;
     bool rust_signed = false;      // SDA_VALUES_RUST_SIGNED: full.rs:30,46-48,62 / chacha.rs:43,88 with Rust's own `%`
+    bool begun = false;            // the combiner's device job (begin_dev .. finish_dev) and its dimension
+    size_t job_dimension = 0;
     int set_value_mode(int mode) {
         if (mode != SDA_VALUES_CANONICAL && mode != SDA_VALUES_RUST_SIGNED) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown value mode %d", mode);
         rust_signed = mode == SDA_VALUES_RUST_SIGNED;
@@ -2167,6 +2174,164 @@ extern "C" int sda_mask_combiner_combine(sda_mask_combiner_t* mc, const int64_t*
     HIP_TRY(hipMemcpyAsync(out, c.d_out.p, dimension * 8, hipMemcpyDeviceToHost, c.ctx.stream));
     SDA_TRY(c.ctx.sync());
     *out_len = dimension;
+    return SDA_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// MaskCombiner, device form (receive.rs:101-118 with the masks in HBM): begin / update / finish, every update stream-ordered
+// -------------------------------------------------------------------------------------------------
+namespace {
+// head of the plan scratch (MaskCore::d_list): three counters the kernels keep, then the two lists of a chunk
+enum { PLAN_SHIFT = 0, PLAN_EXACT = 1, PLAN_KEYS = 2, PLAN_HEAD = 4 };
+constexpr size_t kMaskChunk = (size_t)1 << 20;             // seeds per launch, as chacha_accumulate
+
+int mask_chunk_scratch(MaskCore& c, size_t ns, hipStream_t s) {
+    SDA_TRY(c.d_seeds.reserve_wiped(ns * 32));
+    SDA_TRY(c.d_flags.reserve(ns * sizeof(RejectRecord)));
+    SDA_TRY(c.d_list.reserve((PLAN_HEAD + 2 * ns) * 4));
+    HIP_TRY(hipMemsetAsync(c.d_list.p, 0, PLAN_HEAD * 4, s));
+    return SDA_OK;
+}
+
+// chacha_accumulate for the ns (counted: at most ns, PLAN_KEYS of them) keys in c.d_seeds, with the repair plan made and read on
+// the device: fast pass, plan, list-driven shift and exact-order launches - or exact order for all when rejections are the rule,
+// which (modulus, dimension) alone decide
+int chacha_accumulate_dev(MaskCore& c, size_t ns, bool counted, hipStream_t s) {
+    const size_t dimension = c.job_dimension;
+    if (ns == 0 || dimension == 0) return SDA_OK;
+    const uint64_t zone = rand03_zone(c.mod.m);
+    const double p_rej = (double)(UINT64_MAX - zone + 1) / 18446744073709551616.0;
+    const bool all_slow = p_rej * (double)dimension > 1.0 || dimension >= 0xFFFFFFF0ull;
+    const uint32_t* keys = c.d_seeds.as<uint32_t>();
+    uint32_t* plan = c.d_list.as<uint32_t>();
+    uint64_t* lo = c.acc.lo.as<uint64_t>();
+    int64_t* hi = c.acc.hi.as<int64_t>();
+    if (all_slow) {
+        if (counted) HIP_TRY(launch_chacha_mask_slow_listed(keys, nullptr, plan + PLAN_KEYS, ns, dimension, c.mod, zone, lo, hi, false, s));
+        else HIP_TRY(launch_chacha_mask_slow(keys, nullptr, ns, dimension, c.mod, zone, lo, hi, false, s));
+        return SDA_OK;
+    }
+    RejectRecord* rej = c.d_flags.as<RejectRecord>();
+    HIP_TRY(hipMemsetAsync(rej, 0, ns * sizeof(RejectRecord), s));
+    if (counted) HIP_TRY(launch_chacha_mask_accumulate_counted(keys, plan + PLAN_KEYS, ns, dimension, c.mod, zone, lo, hi, rej, s));
+    else HIP_TRY(launch_chacha_mask_accumulate(keys, ns, dimension, c.mod, zone, lo, hi, rej, s));
+    uint32_t* shift = plan + PLAN_HEAD;
+    uint32_t* exact = shift + ns;
+    HIP_TRY(launch_chacha_mask_plan(rej, ns, plan, shift, exact, s));
+    HIP_TRY(launch_chacha_mask_shift_listed(keys, shift, plan + PLAN_SHIFT, ns, rej, dimension, zone, lo, hi, s));
+    HIP_TRY(launch_chacha_mask_slow_listed(keys, exact, plan + PLAN_EXACT, ns, dimension, c.mod, zone, lo, hi, true, s));
+    return SDA_OK;
+}
+const char* const kMaskRepairKernels = "chacha_mask_plan_kernel + chacha_mask_shift_listed_kernel + chacha_mask_slow_listed_kernel";
+}  // namespace
+
+extern "C" int sda_mask_combiner_begin_dev(sda_mask_combiner_t* mc, size_t dimension, void* stream) {
+    if (!mc) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL");
+    MaskCore& c = mc->core;
+    if (c.scheme.kind == SDA_MASKING_NONE) {                                  // none.rs:21-26: nothing to sum, no device
+        c.begun = true; c.job_dimension = dimension;
+        return SDA_OK;
+    }
+    if (c.scheme.kind == SDA_MASKING_CHACHA && dimension != c.scheme.dimension)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "dimension %zu is not the scheme's (%llu): the result has the configured dimension, chacha.rs:58",
+                    dimension, (unsigned long long)c.scheme.dimension);
+    SDA_TRY(c.ctx.use());
+    // full.rs:46-48 is the combiner's loop in either representation; every ChaCha mask is >= 0 and the running value starts at
+    // 0, so both value modes give the same numbers there (as in the host form)
+    c.acc.rust_signed = c.scheme.kind == SDA_MASKING_FULL && c.rust_signed;
+    c.acc.q = (int64_t)c.mod.m;
+    SDA_TRY(c.acc.reset(dimension, c.ctx.pick(stream)));
+    c.begun = true; c.job_dimension = dimension;
+    return SDA_OK;
+}
+
+extern "C" int sda_mask_combiner_update_dev(sda_mask_combiner_t* mc, const int64_t* d_rows, size_t rows, size_t row_len,
+                                            size_t row_stride, void* stream) {
+    if (!mc) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL");
+    MaskCore& c = mc->core;
+    if (!c.begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (rows == 0) return SDA_OK;
+    if (c.scheme.kind == SDA_MASKING_NONE) {
+        if (row_len != 0) return fail(SDA_ERR_ASSERTION, "assertion failed: masks.iter().all(|mask| mask.len() == 0) - none.rs:23");
+        return SDA_OK;
+    }
+    if (c.scheme.kind == SDA_MASKING_FULL && row_len != c.job_dimension)
+        return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (mask length) - full.rs:43");
+    if (row_len > 0 && !d_rows) return fail(SDA_ERR_INVALID_ARGUMENT, "d_rows is NULL");
+    if (row_stride < row_len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < row_len");
+    if (c.job_dimension == 0) return SDA_OK;
+    SDA_TRY(c.ctx.use());
+    hipStream_t s = c.ctx.pick(stream);
+    if (c.scheme.kind == SDA_MASKING_FULL)                                    // full.rs:37-52
+        return acc_update(c.acc, d_rows, 1, 0, rows, row_stride, c.job_dimension, s);
+    // ChaCha - chacha.rs:60-73: a row is a seed
+    for (size_t r0 = 0; r0 < rows; r0 += kMaskChunk) {
+        const size_t ns = std::min(kMaskChunk, rows - r0);
+        SDA_TRY(mask_chunk_scratch(c, ns, s));
+        HIP_TRY(launch_mask_rows_to_keys(d_rows + r0 * row_stride, ns, row_len, row_stride, c.d_seeds.as<uint32_t>(), s));
+        SDA_TRY(chacha_accumulate_dev(c, ns, false, s));
+    }
+    note_kernel("mask_rows_to_keys_kernel + chacha_mask_fast_kernel + %s", kMaskRepairKernels);          // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return SDA_OK;
+}
+
+extern "C" int sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* mc, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                        const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
+                                                        size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows,
+                                                        size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status, void* stream) {
+    if (!mc) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    MaskCore& c = mc->core;
+    if (c.scheme.kind == SDA_MASKING_NONE)                                    // a None mask is empty: there is no box to open
+        return c.begun ? fail(SDA_ERR_UNSUPPORTED, "the None scheme has no masks to unseal (none.rs:21-26)") : fail(SDA_ERR_STATE, "update before begin");
+    if (!codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!c.begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (c.acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update_dev");
+    if (rows == 0) return SDA_OK;
+    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
+    SDA_TRY(c.ctx.use());
+    hipStream_t s = c.ctx.pick(stream);
+    const SboxState* d_states = nullptr;
+    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, c.ctx.device, s,
+                                       &d_states));
+    if (c.scheme.kind == SDA_MASKING_FULL) {                                  // a row is a mask vector: the clerk's sealed sum
+        int waves = 0;
+        HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, c.job_dimension,
+                                             c.acc.lo.as<uint64_t>(), c.acc.hi.as<int64_t>(), d_status, s, &waves));
+        note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
+        snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+        return SDA_OK;
+    }
+    // ChaCha: a row is the varint encoding of a seed (sodium.rs:36-43).  With dimension 0 the rows are still verified and decoded
+    for (size_t r0 = 0; r0 < rows; r0 += kMaskChunk) {
+        const size_t ns = std::min(kMaskChunk, rows - r0);
+        SDA_TRY(mask_chunk_scratch(c, ns, s));
+        uint32_t* plan = c.d_list.as<uint32_t>();
+        HIP_TRY(launch_sealed_seed_keys(d_boxes + r0 * slot_bytes, slot_bytes, d_row_bytes + r0, ns, max_box_bytes, d_states + r0,
+                                        c.d_seeds.as<uint32_t>(), plan + PLAN_KEYS, d_status, s));
+        SDA_TRY(chacha_accumulate_dev(c, ns, true, s));
+    }
+    note_kernel("sbox_poly_kernel + sealed_seed_keys_kernel + chacha_mask_fast_counted_kernel + %s", kMaskRepairKernels);
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return SDA_OK;
+}
+
+extern "C" int sda_mask_combiner_finish_dev(sda_mask_combiner_t* mc, int64_t* d_out, size_t out_cap, void* stream) {
+    if (!mc) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL");
+    MaskCore& c = mc->core;
+    if (!c.begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (c.scheme.kind == SDA_MASKING_NONE) { c.begun = false; return SDA_OK; }
+    const size_t dimension = c.job_dimension;
+    if (dimension > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_cap < dimension) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(c.ctx.use());
+    hipStream_t s = c.ctx.pick(stream);
+    if (dimension) SDA_TRY(acc_finish(c.acc, dimension, c.mod, d_out, s));
+    if (c.d_seeds.p) HIP_TRY(hipMemsetAsync(c.d_seeds.p, 0, c.d_seeds.cap, s));   // the job's last keys
+    c.begun = false;
     return SDA_OK;
 }
 

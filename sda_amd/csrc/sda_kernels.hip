@@ -21,6 +21,7 @@
 #include "clerk_sum.hpp"
 #include "kernels.hpp"
 #include "modarith.hpp"
+#include "sbox_primitives.hpp"
 #include "signed_rem.hpp"
 
 namespace sda {
@@ -1408,12 +1409,9 @@ __global__ __launch_bounds__(kThreads) void full_mask_drbg_kernel(const int64_t*
 //     mask index), one lane owns 8 output positions and loops over seeds; a rejected candidate
 //     flags its seed, and flagged seeds are corrected by the exact sequential-order slow kernel.
 // =================================================================================================
-__global__ __launch_bounds__(kThreads) void chacha_mask_fast_kernel(const uint32_t* __restrict__ seeds,
-                                                                    size_t n_seeds, size_t dimension, ModParams mod,
-                                                                    uint64_t zone, uint64_t* __restrict__ acc_lo,
-                                                                    int64_t* __restrict__ acc_hi,
-                                                                    RejectRecord* __restrict__ rejects,
-                                                                    size_t seeds_per_split) {
+__device__ __forceinline__ void chacha_fast_body(const uint32_t* __restrict__ seeds, size_t n_seeds, size_t dimension,
+                                                 uint64_t zone, uint64_t* __restrict__ acc_lo, int64_t* __restrict__ acc_hi,
+                                                 RejectRecord* __restrict__ rejects, size_t seeds_per_split) {
     const uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x;   // ChaCha block index
     const size_t pos0 = j * 8;
     if (pos0 >= dimension) return;
@@ -1451,6 +1449,27 @@ __global__ __launch_bounds__(kThreads) void chacha_mask_fast_kernel(const uint32
         if (pos0 + m < dimension) acc_atomic_add(acc_lo + pos0 + m, acc_hi + pos0 + m, lo[m], (int64_t)hi[m]);
 }
 
+__global__ __launch_bounds__(kThreads) void chacha_mask_fast_kernel(const uint32_t* __restrict__ seeds,
+                                                                    size_t n_seeds, size_t dimension, ModParams mod,
+                                                                    uint64_t zone, uint64_t* __restrict__ acc_lo,
+                                                                    int64_t* __restrict__ acc_hi,
+                                                                    RejectRecord* __restrict__ rejects,
+                                                                    size_t seeds_per_split) {
+    (void)mod;
+    chacha_fast_body(seeds, n_seeds, dimension, zone, acc_lo, acc_hi, rejects, seeds_per_split);
+}
+
+// the same pass over a key array whose length lives on the device (the sealed seed rows that passed, mask combiner's device
+// form): the grid is sized for the host's upper bound, a split past *n_keys has an empty seed loop
+__global__ __launch_bounds__(kThreads) void chacha_mask_fast_counted_kernel(const uint32_t* __restrict__ seeds,
+                                                                            const uint32_t* __restrict__ n_keys, size_t dimension,
+                                                                            uint64_t zone, uint64_t* __restrict__ acc_lo,
+                                                                            int64_t* __restrict__ acc_hi,
+                                                                            RejectRecord* __restrict__ rejects,
+                                                                            size_t seeds_per_split) {
+    chacha_fast_body(seeds, *n_keys, dimension, zone, acc_lo, acc_hi, rejects, seeds_per_split);
+}
+
 // candidate m (0..7) of a ChaCha block, rand 0.3 next_u64 = (word 2m << 32) | word 2m+1
 __device__ __forceinline__ uint64_t block_candidate(const uint32_t (&o)[16], uint32_t m) {
     uint32_t hi = 0, lo = 0;
@@ -1475,13 +1494,10 @@ struct MaskApply {
 };
 
 template <bool APPLY>
-__global__ __launch_bounds__(kThreads) void chacha_mask_shift_kernel(const uint32_t* __restrict__ seeds,
-                                                                     const uint32_t* __restrict__ list,
-                                                                     const RejectRecord* __restrict__ rejects,
-                                                                     size_t dimension, uint64_t zone,
-                                                                     uint64_t* __restrict__ acc_lo,
-                                                                     int64_t* __restrict__ acc_hi, MaskApply ap) {
-    const uint32_t s = list[blockIdx.y];
+__device__ __forceinline__ void chacha_shift_body(const uint32_t* __restrict__ seeds, const uint32_t s,
+                                                  const RejectRecord* __restrict__ rejects, size_t dimension, uint64_t zone,
+                                                  uint64_t* __restrict__ acc_lo, int64_t* __restrict__ acc_hi,
+                                                  const MaskApply& ap) {
     const uint32_t R = rejects[s].count;                                  // 1..3 by construction of the list
     uint32_t x0 = rejects[s].pos[0], x1 = R > 1 ? rejects[s].pos[1] : 0xFFFFFFFFu, x2 = R > 2 ? rejects[s].pos[2] : 0xFFFFFFFFu;
     if (x0 > x1) { const uint32_t t = x0; x0 = x1; x1 = t; }
@@ -1534,6 +1550,30 @@ __global__ __launch_bounds__(kThreads) void chacha_mask_shift_kernel(const uint3
     }
 }
 
+template <bool APPLY>
+__global__ __launch_bounds__(kThreads) void chacha_mask_shift_kernel(const uint32_t* __restrict__ seeds,
+                                                                     const uint32_t* __restrict__ list,
+                                                                     const RejectRecord* __restrict__ rejects,
+                                                                     size_t dimension, uint64_t zone,
+                                                                     uint64_t* __restrict__ acc_lo,
+                                                                     int64_t* __restrict__ acc_hi, MaskApply ap) {
+    chacha_shift_body<APPLY>(seeds, list[blockIdx.y], rejects, dimension, zone, acc_lo, acc_hi, ap);
+}
+
+// ... driven by a list whose LENGTH lives on the device (mask combiner's device form: the host never learns how many seeds
+// need the repair): a fixed grid, workgroup row y takes entries y, y + gridDim.y, ... below *n_list - none for an empty list
+__global__ __launch_bounds__(kThreads) void chacha_mask_shift_listed_kernel(const uint32_t* __restrict__ seeds,
+                                                                            const uint32_t* __restrict__ list,
+                                                                            const uint32_t* __restrict__ n_list,
+                                                                            const RejectRecord* __restrict__ rejects,
+                                                                            size_t dimension, uint64_t zone,
+                                                                            uint64_t* __restrict__ acc_lo,
+                                                                            int64_t* __restrict__ acc_hi) {
+    const uint32_t n = *n_list;
+    for (uint32_t e = blockIdx.y; e < n; e += gridDim.y)
+        chacha_shift_body<false>(seeds, list[e], rejects, dimension, zone, acc_lo, acc_hi, MaskApply{});
+}
+
 // APPLY fast pass: participant s = blockIdx.y of the slice, one lane = one ChaCha block = 8 positions
 __global__ __launch_bounds__(kThreads) void chacha_mask_apply_kernel(const uint32_t* __restrict__ seeds, size_t dimension,
                                                                      uint64_t zone, RejectRecord* __restrict__ rejects,
@@ -1562,15 +1602,10 @@ __global__ __launch_bounds__(kThreads) void chacha_mask_apply_kernel(const uint3
 // exact expansion for the listed seeds; one workgroup per seed walks the candidate stream in order.
 // With subtract_naive the fast kernel's "candidate i -> position i" contribution is taken back.
 template <bool APPLY>
-__global__ __launch_bounds__(kThreads) void chacha_mask_slow_kernel(const uint32_t* __restrict__ seeds,
-                                                                    const uint32_t* __restrict__ list, size_t dimension,
-                                                                    ModParams mod, uint64_t zone,
-                                                                    uint64_t* __restrict__ acc_lo,
-                                                                    int64_t* __restrict__ acc_hi, bool subtract_naive,
-                                                                    MaskApply ap) {
-    __shared__ uint32_t wave_tot[kThreads / 64];
-    __shared__ uint32_t chunk_total;
-    const uint32_t s = list ? list[blockIdx.x] : blockIdx.x;
+__device__ __forceinline__ void chacha_slow_body(const uint32_t* __restrict__ seeds, const uint32_t s, size_t dimension,
+                                                 const ModParams& mod, uint64_t zone, uint64_t* __restrict__ acc_lo,
+                                                 int64_t* __restrict__ acc_hi, bool subtract_naive, const MaskApply& ap,
+                                                 uint32_t* wave_tot, uint32_t& chunk_total) {
     uint32_t key[8];
 #pragma unroll
     for (int w = 0; w < 8; ++w) key[w] = seeds[(size_t)s * 8 + w];
@@ -1624,6 +1659,111 @@ __global__ __launch_bounds__(kThreads) void chacha_mask_slow_kernel(const uint32
         block_base += kThreads;
         __syncthreads();
     }
+}
+
+template <bool APPLY>
+__global__ __launch_bounds__(kThreads) void chacha_mask_slow_kernel(const uint32_t* __restrict__ seeds,
+                                                                    const uint32_t* __restrict__ list, size_t dimension,
+                                                                    ModParams mod, uint64_t zone,
+                                                                    uint64_t* __restrict__ acc_lo,
+                                                                    int64_t* __restrict__ acc_hi, bool subtract_naive,
+                                                                    MaskApply ap) {
+    __shared__ uint32_t wave_tot[kThreads / 64];
+    __shared__ uint32_t chunk_total;
+    chacha_slow_body<APPLY>(seeds, list ? list[blockIdx.x] : blockIdx.x, dimension, mod, zone, acc_lo, acc_hi, subtract_naive, ap,
+                            wave_tot, chunk_total);
+}
+
+// ... over a list (nullptr: keys 0 .. *n_list - 1) whose length lives on the device: a fixed grid, workgroup x walks entries
+// x, x + gridDim.x, ... one after the other (every walk ends on a barrier, so the shared scan words are free again)
+__global__ __launch_bounds__(kThreads) void chacha_mask_slow_listed_kernel(const uint32_t* __restrict__ seeds,
+                                                                           const uint32_t* __restrict__ list,
+                                                                           const uint32_t* __restrict__ n_list, size_t dimension,
+                                                                           ModParams mod, uint64_t zone,
+                                                                           uint64_t* __restrict__ acc_lo,
+                                                                           int64_t* __restrict__ acc_hi, bool subtract_naive) {
+    __shared__ uint32_t wave_tot[kThreads / 64];
+    __shared__ uint32_t chunk_total;
+    const uint32_t n = *n_list;
+    for (uint32_t e = blockIdx.x; e < n; e += gridDim.x)
+        chacha_slow_body<false>(seeds, list ? list[e] : e, dimension, mod, zone, acc_lo, acc_hi, subtract_naive, MaskApply{},
+                                wave_tot, chunk_total);
+}
+
+// ---- the mask combiner's device form (chacha.rs:56-77 with nothing on the host) ----------------------------------------
+// seed rows -> ChaCha keys: row r of [rows][row_len] int64 (stride row_stride), words used `as u32` (chacha.rs:62-64), at most 8
+// (rand 0.3 from_seed), missing ones 0 - seed_to_key of the host form; one lane per key word
+__global__ __launch_bounds__(kThreads) void mask_rows_to_keys_kernel(const int64_t* __restrict__ rows, size_t n_rows, size_t row_len,
+                                                                     size_t row_stride, uint32_t* __restrict__ keys) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n_rows * 8) return;
+    const size_t r = i >> 3, w = i & 7;
+    keys[i] = w < row_len ? (uint32_t)(uint64_t)rows[r * row_stride + w] : 0u;
+}
+
+// the repair plan of a chunk after its fast pass: seed i with 1..3 recorded rejections joins the shift list, with more the
+// exact-order list; plan[0] / plan[1] count them (zeroed by the caller).  The order inside a list is whatever the atomics
+// give - the sums are exact integers, so the result does not depend on it
+__global__ __launch_bounds__(kThreads) void chacha_mask_plan_kernel(const RejectRecord* __restrict__ rejects, size_t n,
+                                                                    uint32_t* __restrict__ plan, uint32_t* __restrict__ shift_list,
+                                                                    uint32_t* __restrict__ exact_list) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t c = rejects[i].count;
+    if (c == 0) return;
+    if (c <= 3) shift_list[atomicAdd(&plan[0], 1u)] = (uint32_t)i;
+    else exact_list[atomicAdd(&plan[1], 1u)] = (uint32_t)i;
+}
+
+// sealed seed rows -> ChaCha keys (receive.rs:101-118 for a ChaCha mask: open the box, decode_var the seed words, chacha.rs:62-64).
+// Box r at boxes + r * slot (epk 32 | tag 16 | ciphertext) has been through the sealed-box verify pass; a row whose state says
+// `bad` is skipped, so no byte of an unauthenticated box is decrypted.  One lane per row: a seed is a few dozen bytes, the lane
+// xors the XSalsa20 keystream (message byte m = stream byte 32 + m) into them one at a time and walks the zig-zag LEB128 values in
+// registers - only the low 35 bits of a value can reach its `as u32` word, words past the eighth are walked for validity and
+// dropped.  A row that ends inside a value (status 4) or holds a value of more than 10 bytes (status 1) gives no key.  The keys of
+// the rows that pass are packed at keys[8 * k], k from an atomic counter: a row that failed is never expanded.
+__global__ __launch_bounds__(kThreads) void sealed_seed_keys_kernel(const uint8_t* __restrict__ boxes, uint64_t slot,
+                                                                    const uint64_t* __restrict__ row_bytes, uint64_t max_box,
+                                                                    const SboxState* __restrict__ states, uint64_t rows,
+                                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ n_keys,
+                                                                    uint32_t* __restrict__ status) {
+    const uint64_t r = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= rows) return;
+    const uint64_t have = row_bytes[r];
+    if (have < 48 || have > max_box || have > slot || states[r].bad) return;       // the length is tested again: a row never leaves its slot
+    const uint8_t* ct = boxes + r * slot + 48;
+    const uint64_t mlen = have - 48;
+    uint32_t sub[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sub[i] = states[r].subkey[i];
+    const uint32_t n0 = states[r].n0, n1 = states[r].n1;
+    uint32_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t ks[16];
+    uint64_t zz = 0;
+    uint32_t nb = 0, words = 0, flags = 0;
+    for (uint64_t m = 0; m < mlen; ++m) {
+        const uint64_t sp = m + 32;
+        if (m == 0 || (sp & 63) == 0) sbx::salsa20_block(ks, sub, n0, n1, sp >> 6);
+        uint32_t word = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 16; ++w) word = ((uint32_t)(sp >> 2) & 15u) == w ? ks[w] : word;
+        const uint32_t b = (ct[m] ^ (word >> (8 * (uint32_t)(sp & 3)))) & 0xFFu;
+        if (nb < 5) zz |= (uint64_t)(b & 0x7Fu) << (7 * nb);
+        ++nb;
+        if (!(b & 0x80u)) {
+            if (nb > 10) flags |= 1u;
+            const uint32_t v = (uint32_t)((zz >> 1) ^ (0 - (zz & 1)));
+#pragma unroll
+            for (uint32_t w = 0; w < 8; ++w) key[w] = w == words ? v : key[w];
+            if (words < 8) ++words;
+            zz = 0; nb = 0;
+        }
+    }
+    if (nb != 0) flags = 4u;                                                   // the row was never streamed by the decoder either
+    if (flags) { atomicOr(status, flags); return; }
+    const uint32_t k = atomicAdd(n_keys, 1u);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) keys[(size_t)k * 8 + w] = key[w];
 }
 
 // =================================================================================================
@@ -2396,6 +2536,81 @@ hipError_t launch_chacha_mask_slow(const uint32_t* d_seeds, const uint32_t* d_li
     if (hipError_t e = grid_check(n_list)) return e;
     chacha_mask_slow_kernel<false><<<dim3((unsigned)n_list), dim3(kThreads), 0, s>>>(d_seeds, d_list, dimension, mod, zone,
                                                                                      d_acc_lo, d_acc_hi, subtract_naive, MaskApply{});
+    return hipGetLastError();
+}
+
+// ---- the mask combiner's device form: nothing below waits for the device or learns a count from it --------------------
+hipError_t launch_mask_rows_to_keys(const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride, uint32_t* d_keys,
+                                    hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const uint64_t blocks = ceil_div(rows * 8, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    mask_rows_to_keys_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_rows, rows, row_len, row_stride, d_keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_sealed_seed_keys(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
+                                   const SboxState* d_states, uint32_t* d_keys, uint32_t* d_n_keys, uint32_t* d_status, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const uint64_t blocks = ceil_div(rows, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    sealed_seed_keys_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_boxes, slot, d_row_bytes, max_box_bytes, d_states, rows,
+                                                                            d_keys, d_n_keys, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_chacha_mask_accumulate_counted(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
+                                                 const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
+                                                 RejectRecord* d_rejects, hipStream_t s) {
+    (void)mod;
+    if (max_seeds == 0 || dimension == 0) return hipSuccess;
+    const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
+    if (hipError_t e = grid_check(pos_blocks)) return e;
+    const uint64_t want_blocks = 256 * 8;                  // the split of launch_chacha_mask_accumulate, for the upper bound
+    uint64_t split = 1;
+    if (pos_blocks < want_blocks) split = ceil_div(want_blocks, pos_blocks);
+    if (split > max_seeds) split = max_seeds;
+    if (split > 65535) split = 65535;
+    const size_t per = ceil_div(max_seeds, split);
+    split = ceil_div(max_seeds, per);
+    chacha_mask_fast_counted_kernel<<<dim3((unsigned)pos_blocks, (unsigned)split), dim3(kThreads), 0, s>>>(
+        d_seeds, d_n_seeds, dimension, zone, d_acc_lo, d_acc_hi, d_rejects, per);
+    return hipGetLastError();
+}
+
+hipError_t launch_chacha_mask_plan(const RejectRecord* d_rejects, size_t n, uint32_t* d_plan, uint32_t* d_shift_list,
+                                   uint32_t* d_exact_list, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = ceil_div(n, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    chacha_mask_plan_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_rejects, n, d_plan, d_shift_list, d_exact_list);
+    return hipGetLastError();
+}
+
+// The list dimension of the grid is capped: about 4096 workgroups in all (an empty list costs that many that return after one
+// scalar load), never fewer than 16 list rows nor more than the list can hold
+hipError_t launch_chacha_mask_shift_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
+                                           const RejectRecord* d_rejects, size_t dimension, uint64_t zone, uint64_t* d_acc_lo,
+                                           int64_t* d_acc_hi, hipStream_t s) {
+    if (max_list == 0 || dimension == 0) return hipSuccess;
+    const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
+    if (hipError_t e = grid_check(pos_blocks)) return e;
+    uint64_t gy = 4096 / pos_blocks;
+    if (gy < 16) gy = 16;
+    if (gy > 65535) gy = 65535;
+    if (gy > max_list) gy = max_list;
+    chacha_mask_shift_listed_kernel<<<dim3((unsigned)pos_blocks, (unsigned)gy), dim3(kThreads), 0, s>>>(
+        d_seeds, d_list, d_n_list, d_rejects, dimension, zone, d_acc_lo, d_acc_hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_chacha_mask_slow_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
+                                          size_t dimension, const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo,
+                                          int64_t* d_acc_hi, bool subtract_naive, hipStream_t s) {
+    if (max_list == 0 || dimension == 0) return hipSuccess;
+    const unsigned grid = (unsigned)(max_list < 2048 ? max_list : 2048);
+    chacha_mask_slow_listed_kernel<<<dim3(grid), dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, dimension, mod, zone, d_acc_lo,
+                                                                         d_acc_hi, subtract_naive);
     return hipGetLastError();
 }
 

@@ -344,6 +344,21 @@ struct MaskCombiner {
         out.resize(n_out);
         return out;
     }
+    // the same sums as a streaming job on device-resident rows (receive.rs:101-118); nothing here synchronises the stream
+    void begin_dev(size_t dimension, void* stream = nullptr) { detail::check(sda_mask_combiner_begin_dev(h, dimension, stream)); }
+    void update_dev(const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride, void* stream = nullptr) {
+        detail::check(sda_mask_combiner_update_dev(h, d_rows, rows, row_len, row_stride, stream));
+    }
+    // the participants' sealed mask encryptions, laid out as for sda_sealedbox_open_rows_dev; *d_status != 0: do not use the result
+    void update_sealed_rows_dev(ShareCodec& codec, SealedBox& box, const EncryptionKey& pk, const DecryptionKey& sk,
+                                const uint8_t* d_boxes, size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows,
+                                size_t max_box_bytes, uint32_t* d_status, uint32_t* d_ok = nullptr, void* stream = nullptr) {
+        detail::check(sda_mask_combiner_update_sealed_rows_dev(h, codec.h, box.h, pk.data(), sk.data(), d_boxes, slot_bytes, d_row_bytes,
+                                                               rows, max_box_bytes, d_ok, d_status, stream));
+    }
+    void finish_dev(int64_t* d_out, size_t out_cap, void* stream = nullptr) {
+        detail::check(sda_mask_combiner_finish_dev(h, d_out, out_cap, stream));
+    }
 };
 
 struct SecretUnmasker {
