@@ -14,7 +14,8 @@ def _edge_values():
          2 ** 63 - 1, -2 ** 63, -2 ** 63 + 1]
     for b in range(0, 64, 7):
         e += [2 ** b, 2 ** b - 1, -(2 ** b), -(2 ** b) - 1] if b < 63 else []
-    return np.array(e, dtype=np.int64)
+    from varint_limits import LENGTH_EDGES                  # both ends of every bit length of the zig-zag word: |v| = 2^(7k-1) included
+    return np.array(e + LENGTH_EDGES, dtype=np.int64)
 
 
 def test_published_vectors(gpu):
