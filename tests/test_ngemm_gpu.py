@@ -316,10 +316,10 @@ def test_narrow_limb_gemm_rejected_draw_pairs_are_redone_from_the_retry_stream(g
     from sda_amd.capi import check
     from sda_amd.device import DeviceBuffer
     from oracle import coracle
-    p, k, t, n = 8211457, 40, 23, 242
-    assert p <= 0x7F7F7F and (p - 1) % 64 == 0 and (p - 1) % 243 == 0
+    from drbg_retry import NGEMM_VOLUME as V        # the job's parameters live there: tests/test_drbg_retry_reach.py locates its rejections
+    p, k, t, n, P, B, first = V["p"], V["k"], V["t"], V["n"], V["participants"], V["batches"], V["first"]
+    assert V["key"] == KEY and p <= 0x7F7F7F and (p - 1) % 64 == 0 and (p - 1) % 243 == 0
     w2, w3 = _root(p, 64), _root(p, 243)
-    P, B = 2, 500_000
     dim = k * B
     expected_rejections = ((1 << 64) % (p * p)) / 2.0 ** 64 * P * B * ((t + 1) // 2)
     assert expected_rejections > 30, expected_rejections
@@ -330,10 +330,10 @@ def test_narrow_limb_gemm_rejected_draw_pairs_are_redone_from_the_retry_stream(g
     secrets = DeviceBuffer(P * dim)
     check(gpu.sda_fill_synthetic_dev(secrets.ptr, P, dim, dim, 0, 77, p, None))
     out = DeviceBuffer(n * P * B)
-    gen.generate_batch_dev(secrets.ptr, P, dim, dim, out.ptr, B, P * B, first_participant=5)
+    gen.generate_batch_dev(secrets.ptr, P, dim, dim, out.ptr, B, P * B, first_participant=first)
     assert gpu.sda_debug_last_kernel().decode() == "packed_gen_ngemm_kernel<1, 4>"
     for q in range(P):
-        want = coracle.drbg_fill(KEY, 5 + q, B, t, p).reshape(B, t)
+        want = coracle.drbg_fill(KEY, first + q, B, t, p).reshape(B, t)
         for i in range(t):
             got = out.to_numpy(B, (i * P + q) * B)
             bad = np.flatnonzero(got != want[:, i])

@@ -485,6 +485,14 @@ def test_drbg_rejection_path(gpu):
     got2 = gen.generate(np.zeros(dim, dtype=np.int64))       # stream 1: fresh randomness per call
     assert np.array_equal(got2[:2], coracle.drbg_fill(KEY, 1, dim, 2, m).reshape(dim, 2).T)
     assert not np.array_equal(got, got2)
+    # a stream id above 2^32: word 15 of a retry block carries the id's top 24 bits under the attempt number
+    from sda_amd.device import DeviceBuffer
+    first, Bs = (0xB00F << 32) + 7, dim + 1
+    d_sec = DeviceBuffer.from_numpy(np.zeros(Bs, dtype=np.int64))
+    d_out = DeviceBuffer(3 * Bs).zero()
+    gen.generate_batch_dev(d_sec.ptr, 1, dim, Bs, d_out.ptr, 3 * Bs, Bs, first_participant=first)
+    got3 = d_out.to_numpy().reshape(3, Bs)[:2, :dim]
+    assert np.array_equal(got3, coracle.drbg_fill(KEY, first, dim, 2, m).reshape(dim, 2).T)
 
 
 @pytest.mark.parametrize("m,T", [(8355709, 2), (0x7F7F7F, 3), (5038849, 5)])
