@@ -369,6 +369,48 @@ int sda_secret_reconstructor_reconstruct_dev(sda_secret_reconstructor_t* r,
                                              int64_t* d_out, size_t out_cap, size_t* out_len,
                                              void* stream);
 
+/* reconstruct() as a streaming job on the device - the second half of the recipient's reveal, client/src/receive.rs:120-146
+ * (decrypt every clerking result, then reconstruct), with the results in HBM; mirrors sda_mask_combiner_begin_dev / update_dev
+ * / finish_dev.  Packed reconstruction is a fixed k x n' matrix R per clerk-index set, so
+ *     secret[b*k + s] = sum over rows i of R[s][i] * share_i[b] mod q
+ * is a weighted clerk sum: a clerking result is folded in when it lands, alone, in any order, and need not be kept.  Any number
+ * of update calls of either form (the sealed one is declared with the sealed boxes below) may come between begin_dev and
+ * finish_dev, in any order, freely mixed; rows == 0 is SDA_OK and launches nothing; update / finish before begin ->
+ * SDA_ERR_STATE; a NULL handle or pointer -> SDA_ERR_INVALID_ARGUMENT before anything touches a device.  NO UPDATE CALL
+ * SYNCHRONISES THE STREAM OR COPIES ANYTHING TO THE HOST: everything is enqueued on `stream` (NULL: the handle's), so d_shares /
+ * d_boxes may be reused as soon as later work on the same stream overwrites them.  The job has sums and a matrix of its own:
+ * reconstruct / reconstruct_dev calls on the same handle do not disturb it.  One stream at a time per handle.  The value mode is
+ * read at begin_dev.
+ *
+ *   begin_dev : declares the whole index set: indices[i] (host) is the clerk index of position i, row_len the number of values
+ *               every row holds.  PackedShamir: n_rows < t + k -> SDA_ERR_NOT_ENOUGH_SHARES (packed_shamir.rs:75); row_len <
+ *               ceil(dimension / k) -> SDA_ERR_ASSERTION (batched.rs:84); colliding indices -> SDA_ERR_INVALID_ARGUMENT, as
+ *               reconstruct; values past the first ceil(dimension / k) of a row are decoded for validity and otherwise ignored.
+ *               Additive: indices may be NULL and is ignored, the output length is row_len.  At most 65535 rows.  MAY
+ *               SYNCHRONISE the stream (the matrix is built on the host and uploaded); zeroes ceil(dimension / k) * k
+ *               128-bit accumulators (Additive: row_len).  A begin_dev refused for its arguments (the errors above) leaves a
+ *               job already in flight on the handle as it was; one that passes them replaces it.
+ *   update_dev: positions first_pos .. first_pos + rows - 1 from decoded rows [rows][row_len] int64, row r at d_shares +
+ *               r * row_stride (row_stride >= row_len), any int64 values.  The host keeps a record of fed positions: a position
+ *               fed twice, or >= n_rows, -> SDA_ERR_STATE before any launch.
+ *   finish_dev: an unfed position -> SDA_ERR_STATE; out_cap below the output length -> SDA_ERR_INVALID_ARGUMENT.  Folds the
+ *               accumulators mod q: d_out[0 .. dimension) (Additive: row_len) = bit for bit what
+ *               sda_secret_reconstructor_reconstruct returns for the same rows and indices.  Ends the job: another begin_dev
+ *               may follow.
+ *   Known limit: in the sealed form ONE WAVE streams one row, so a reveal of few, long rows (8 clerks, 1 Mi secrets) has little
+ *   parallelism and may be slower than open_rows_dev + decode_rows_dev + reconstruct_dev; shapes with hundreds of clerks have
+ *   plenty.  Splitting a sealed row between waves needs the terminator count before each split - a second keystream pass.
+ *   Second known limit: the sealed form collects products in an on-chip window of 2048 OUTPUT columns, i.e. 2048 / k values of a
+ *   row.  For k up to about 4 a row's products stay inside it; for large k (k = 100 in the PSS_155 shapes: 20 values) nearly
+ *   every product is added with 128-bit global atomics instead, k per value, and the job is bound by those atomics.  For such
+ *   shapes expect open_rows_dev + decode_rows_dev + reconstruct_dev (or update_dev on decoded rows, which multiplies in
+ *   registers) to be faster; the sealed form's gain there is the footprint, not the time. */
+int sda_secret_reconstructor_begin_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows, size_t row_len,
+                                       void* stream);
+int sda_secret_reconstructor_update_dev(sda_secret_reconstructor_t* r, size_t first_pos, const int64_t* d_shares, size_t rows,
+                                        size_t row_stride, void* stream);
+int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r, int64_t* d_out, size_t out_cap, void* stream);
+
 /* =============================================================================================
  * SecretMasker / MaskCombiner / SecretUnmasker  (masking/mod.rs:9-31; impl none.rs, full.rs, chacha.rs)
  * ============================================================================================= */
@@ -677,6 +719,23 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   SDA_ERR_UNSUPPORTED.  THE REFERENCE FAILS THE WHOLE AGGREGATION on one bad box (sodium.rs:78-80): check
  *                   *d_status before using finish_dev's output.  Uses the sealed-box handle's scratch and the combiner's:
  *                   one stream at a time for both.
+ *
+ *   sda_secret_reconstructor_update_sealed_rows_dev : receive.rs:120-146 from the clerks' sealed results - an update form of
+ *                   the reconstructor's device job (sda_secret_reconstructor_begin_dev above) for positions first_pos ..
+ *                   first_pos + rows - 1 (a position fed twice or >= n_rows -> SDA_ERR_STATE before any launch), rows laid out
+ *                   as for open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does (d_ok[r] when d_ok is given;
+ *                   *d_status |= 16 for a box that does not authenticate, is shorter than 48 or longer than max_box_bytes
+ *                   bytes, or has an all-zero shared secret).  Step 2 streams each row that passed ONCE: keystream, varint
+ *                   decode, the reduction of every value to its canonical residue, the Montgomery multiply by the k
+ *                   coefficients of the row's position and the sums of the k products in one kernel - decrypted bytes exist
+ *                   in registers and LDS only, no plaintext buffer, no decoded tile.  Every row must hold exactly row_len
+ *                   values.  A row that failed step 1 adds nothing and is not decoded.  Status bits 1, 2 and 4 (over-long value,
+ *                   wrong count, unterminated) equal those of open_rows_dev + sda_varint_decode_rows_dev on the boxes that
+ *                   authenticate (that chain also decodes the empty row a refused box leaves and reports 4 for it).  Additive: step
+ *                   2 is the one-pass decrypt + decode + sum of sda_share_combiner_update_sealed_rows_dev on the job's sums.
+ *                   SDA_VALUES_RUST_SIGNED -> SDA_ERR_UNSUPPORTED, as the combiners' wire-fed updates.  THE REFERENCE FAILS THE
+ *                   WHOLE REVEAL on one bad box (sodium.rs:78-80): check *d_status before trusting finish_dev's output.  Uses
+ *                   the sealed-box handle's scratch: one stream at a time for both handles.
  * ============================================================================================= */
 #define SDA_SEALBYTES 48
 typedef struct sda_sealedbox sda_sealedbox_t;
@@ -709,6 +768,12 @@ int  sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* c, sda_varint
                                               const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                               size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
                                               uint32_t* d_ok /* optional */, uint32_t* d_status, void* stream);
+/* receive.rs:120-146: the clerks' sealed results folded into the reconstructor's device job (see above) */
+int  sda_secret_reconstructor_update_sealed_rows_dev(sda_secret_reconstructor_t* r, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                     const uint8_t pk[32], const uint8_t sk[32], size_t first_pos,
+                                                     const uint8_t* d_boxes, size_t slot_bytes, const uint64_t* d_row_bytes,
+                                                     size_t rows, size_t max_box_bytes, uint32_t* d_ok /* optional */,
+                                                     uint32_t* d_status, void* stream);
 
 /* =============================================================================================
  * Cross-GPU modular reduction (new; no reference counterpart - SURVEY.md 8e: the reference's parties meet over HTTP).

@@ -207,6 +207,12 @@ SIGNATURES = {
                                                            C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                            C.c_void_p]),
     "sda_mask_combiner_finish_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sda_secret_reconstructor_begin_dev": (C.c_int, [_H, c_sizep, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "sda_secret_reconstructor_update_dev": (C.c_int, [_H, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "sda_secret_reconstructor_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p,
+                                                                  C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p]),
+    "sda_secret_reconstructor_finish_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sda_comm_unique_id": (C.c_int, [c_u8p]),
     "sda_comm_init": (C.c_int, [c_u8p, C.c_int, C.c_int, _HP]),
     "sda_comm_free": (None, [_H]),

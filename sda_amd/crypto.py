@@ -379,6 +379,64 @@ class SecretReconstructor(_Handle):
                                                                  stream or None))
         return n_out.value
 
+    # streaming device form (receive.rs:120-146 with the clerking results in HBM): no update synchronises or copies to the host
+    def begin_dev(self, indices: Optional[Sequence[int]], n_rows: int, row_len: int, stream: int = 0) -> None:
+        """declares the job: indices[i] is the clerk index of position i (Additive: None), every row holds row_len values"""
+        if indices is not None and len(indices) != n_rows:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {n_rows} rows")
+        cidx = None if indices is None else (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
+        check(self._lib.sda_secret_reconstructor_begin_dev(self._h, cidx, n_rows, row_len, stream or None))
+
+    def update_dev(self, first_pos: int, d_shares: int, rows: int, row_stride: int, stream: int = 0) -> None:
+        """decoded rows in HBM for positions first_pos .. first_pos + rows - 1"""
+        check(self._lib.sda_secret_reconstructor_update_dev(self._h, first_pos, d_shares or None, rows, row_stride, stream or None))
+
+    def update_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", pk: bytes, sk: bytes, first_pos: int, d_boxes: int,
+                               slot_bytes: int, d_row_bytes: int, rows: int, max_box_bytes: int, d_status: int, d_ok: int = 0,
+                               stream: int = 0) -> None:
+        """the same positions from clerking results that are still sealed boxes (the SDAJOBv1 SEALED layout).
+        *d_status & 16: some box failed, the result must not be used (sodium.rs:78-80)"""
+        check(self._lib.sda_secret_reconstructor_update_sealed_rows_dev(self._h, codec._h if codec else None,
+                                                                        box._h if box else None, pk, sk, first_pos,
+                                                                        d_boxes or None, slot_bytes, d_row_bytes or None, rows,
+                                                                        max_box_bytes, d_ok or None, d_status or None,
+                                                                        stream or None))
+
+    def finish_dev(self, d_out: int, out_cap: int, stream: int = 0) -> None:
+        check(self._lib.sda_secret_reconstructor_finish_dev(self._h, d_out or None, out_cap, stream or None))
+
+    def reconstruct_sealed_job(self, blob, indices: Optional[Sequence[int]], pk: bytes, sk: bytes,
+                               row_len: Optional[int] = None) -> np.ndarray:
+        """receive.rs:120-146 for an SDAJOBv1 blob of sealed clerking results, row i from clerk indices[i]: open every one,
+        reconstruct.  One bad box fails the reveal ("Sodium decryption failure"), so does a payload that does not hold
+        row_len values (default: ceil(dimension / k); Additive: the dimension)."""
+        from .device import DeviceBuffer, DeviceBytes
+        job = JobContainer.parse(bytes(blob))
+        L = job.layout
+        if L.payload_kind != capi.JOB_SEALED:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "reconstruct_sealed_job needs a job of sealed boxes (payload kind SEALED)")
+        additive = isinstance(self.scheme, Additive)
+        if row_len is None:
+            row_len = self.dimension if additive else -(-self.dimension // self.scheme.secret_count)
+        n_out = row_len if additive else self.dimension
+        d_out = DeviceBuffer(max(n_out, 1))
+        d_status = DeviceBuffer(1).zero()
+        self.begin_dev(None if additive else indices, L.rows, row_len)
+        if L.rows:
+            d_job = DeviceBytes.from_bytes(job.blob)
+            codec, box = VarintCodec(), SealedBox()
+            self.update_sealed_rows_dev(codec, box, pk, sk, 0, d_job.ptr + L.payload_offset, L.slot_bytes,
+                                        d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status.ptr)
+        self.finish_dev(d_out.ptr, n_out)
+        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
+        if status & 16:
+            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
+        if status & 2:
+            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")
+        if status:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        return d_out.to_numpy()[:n_out].copy()
+
 
 # ---- masking -------------------------------------------------------------------------------------------------
 class SecretMasker(_Handle):

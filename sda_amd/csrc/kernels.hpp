@@ -350,6 +350,24 @@ struct SboxState;
 hipError_t launch_sealed_stream_combine(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
                                         size_t max_box_bytes, const SboxState* d_states, size_t len, uint64_t* d_acc_lo,
                                         int64_t* d_acc_hi, uint32_t* d_status, hipStream_t s, int* waves);
+// A streaming reconstruction job (sda_secret_reconstructor_begin_dev): secret[b k + s] = sum over positions i of
+// Rt[i][s] * share_i[b] mod m, summed exactly into 128-bit accumulators [batches * k] and folded by launch_combine_finish.
+struct WeightedJob {
+    const uint64_t* Rt;      // [n'][k], Montgomery form: row i = the coefficients of position i
+    uint32_t k;
+    uint64_t batches;        // ceil(dimension / k): the values of a row that count
+    uint64_t m, mu, pinv;    // the prime, floor(2^64 / m), -m^{-1} mod 2^64
+};
+// rows that are still sealed boxes (verified by launch_sealedbox_verify; row r is position first_pos + r, holds `len` values):
+// keystream, varint decode, multiply and sums in one pass; 8 rows per workgroup
+hipError_t launch_sealed_stream_weighted(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
+                                         size_t max_box_bytes, const SboxState* d_states, size_t len, size_t first_pos,
+                                         const WeightedJob& J, uint64_t* d_acc_lo, int64_t* d_acc_hi, uint32_t* d_status,
+                                         hipStream_t s);
+// decoded rows [rows][row_stride], row r is position first_pos + r
+hipError_t launch_weighted_rows(const int64_t* d_shares, size_t row_stride, size_t rows, size_t first_pos, const WeightedJob& J,
+                                uint64_t* d_acc_lo, int64_t* d_acc_hi, hipStream_t s);
+hipError_t launch_transpose_u64(const uint64_t* d_in, uint64_t* d_out, uint32_t k, uint32_t n, hipStream_t s);   // [k][n] -> [n][k]
 // share rows -> the ciphertext of their sealed boxes in one pass (varint encode + XSalsa20 keystream, no wire buffer): row r to
 // d_boxes + r * slot_bytes + 48 under d_states[r] (written by launch_sealedbox_seal_setup), its message length to d_msg_bytes[r];
 // a row whose state says `bad` is left alone (length 0)

@@ -1697,6 +1697,16 @@ struct sda_secret_reconstructor {
     bool narrow = false;                 // p < 2^31: the one-limb reveal kernel (d_R31) when the shape and layout allow
     bool no_narrow = false;              // knob SDA_NO_NARROW when the handle was created (a live handle never switches kernels)
     N31Params n31p{};
+    // the streaming job (begin_dev .. finish_dev).  It owns its sums and its copy of the matrix, so reconstruct[_dev] calls on
+    // the same handle between its updates (which reset `acc` and may rebuild d_R for other indices) leave it alone
+    AccState job_acc;
+    DevBuf d_Rt;                         // the job's matrix transposed: [n_rows][k], a position's coefficients contiguous
+    bool job_begun = false;
+    size_t job_rows = 0, job_row_len = 0, job_fed = 0, job_out = 0;
+    std::vector<uint8_t> job_seen;       // positions already fed
+    WeightedJob job() const {
+        return WeightedJob{d_Rt.as<uint64_t>(), k, (uint64_t)((dimension + k - 1) / k), mod.m, mod.mu, mont.pinv};
+    }
 };
 
 extern "C" int sda_secret_reconstructor_new(const sda_sharing_scheme_t* scheme, size_t dimension,
@@ -1736,6 +1746,7 @@ extern "C" void sda_secret_reconstructor_free(sda_secret_reconstructor_t* r) {
     if (!r) return;
     if (r->ctx.device >= 0) (void)hipSetDevice(r->ctx.device);
     r->acc.release(); r->tile.release(); r->d_out.release(); r->d_R.release(); r->d_R31.release(); r->d_shares.release();
+    r->job_acc.release(); r->d_Rt.release();
     r->ctx.destroy();
     delete r;
 }
@@ -1862,6 +1873,117 @@ extern "C" int sda_secret_reconstructor_reconstruct(sda_secret_reconstructor_t* 
     HIP_TRY(hipMemcpyAsync(out, r->d_out.p, n_out * 8, hipMemcpyDeviceToHost, r->ctx.stream));
     SDA_TRY(r->ctx.sync());
     *out_len = n_out;
+    return SDA_OK;
+}
+
+// ---- reconstruct() as a streaming job on the device (receive.rs:120-146 with the clerking results in HBM) ----------------
+// Packed: secret[b k + s] = sum over positions i of R[s][i] * share_i[b] mod q, a weighted clerk sum; the matrix is fixed once
+// the index set is declared, so a row is folded in as soon as it lands.  Additive: the plain clerk sum (additive.rs:55-73).
+extern "C" int sda_secret_reconstructor_begin_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows,
+                                                  size_t row_len, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    size_t n_out = row_len;
+    if (!r->additive) {
+        if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");   // packed_shamir.rs:75
+        if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
+        const size_t batches = (r->dimension + r->k - 1) / r->k;             // batched.rs:77
+        if (row_len < batches) return fail(SDA_ERR_ASSERTION, "share vector shorter than the number of batches (index out of bounds, batched.rs:84)");
+        n_out = batches * r->k;
+    }
+    if (n_rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows");              // the bound the 128-bit sums rest on
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    if (!r->additive) SDA_TRY(prepare_R(r, indices, n_rows, s));            // colliding indices are refused here
+    r->job_begun = false;                     // every argument check has passed: from here on a job in flight is replaced
+    if (!r->additive) {
+        SDA_TRY(r->d_Rt.reserve((size_t)r->k * n_rows * 8));
+        HIP_TRY(launch_transpose_u64(r->d_R.as<uint64_t>(), r->d_Rt.as<uint64_t>(), r->k, (uint32_t)n_rows, s));
+    }
+    r->job_acc.rust_signed = r->acc.rust_signed;                             // the value mode is read here
+    r->job_acc.q = r->acc.q;
+    SDA_TRY(r->job_acc.reset(n_out, s));
+    r->job_seen.assign(n_rows, 0);
+    r->job_rows = n_rows; r->job_row_len = row_len; r->job_fed = 0; r->job_out = r->additive ? row_len : r->dimension;
+    r->job_begun = true;
+    return SDA_OK;
+}
+
+// positions [first_pos, first_pos + rows) are inside the job and not fed yet
+static int job_claim(sda_secret_reconstructor* r, size_t first_pos, size_t rows, bool commit) {
+    if (first_pos >= r->job_rows || rows > r->job_rows - first_pos)
+        return fail(SDA_ERR_STATE, "positions %zu .. %zu: the job was begun with %zu rows", first_pos, first_pos + rows - 1, r->job_rows);
+    for (size_t i = 0; i < rows; ++i)
+        if (r->job_seen[first_pos + i]) return fail(SDA_ERR_STATE, "position %zu was already fed", first_pos + i);
+    if (commit) {
+        for (size_t i = 0; i < rows; ++i) r->job_seen[first_pos + i] = 1;
+        r->job_fed += rows;
+    }
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_reconstructor_update_dev(sda_secret_reconstructor_t* r, size_t first_pos, const int64_t* d_shares,
+                                                   size_t rows, size_t row_stride, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (rows == 0) return SDA_OK;
+    SDA_TRY(job_claim(r, first_pos, rows, false));
+    if (r->job_row_len > 0 && !d_shares) return fail(SDA_ERR_INVALID_ARGUMENT, "d_shares is NULL");
+    if (row_stride < r->job_row_len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < row_len");
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    if (r->additive) {
+        if (r->job_row_len) SDA_TRY(acc_update(r->job_acc, d_shares, 1, 0, rows, row_stride, r->job_row_len, s));    // additive.rs:62-69
+    } else {
+        HIP_TRY(launch_weighted_rows(d_shares, row_stride, rows, first_pos, r->job(), r->job_acc.lo.as<uint64_t>(),
+                                     r->job_acc.hi.as<int64_t>(), s));
+        note_kernel("weighted_rows_kernel");
+    }
+    return job_claim(r, first_pos, rows, true);
+}
+
+extern "C" int sda_secret_reconstructor_update_sealed_rows_dev(sda_secret_reconstructor_t* r, sda_varint_codec_t* codec,
+                                                               sda_sealedbox_t* b, const uint8_t pk[32], const uint8_t sk[32],
+                                                               size_t first_pos, const uint8_t* d_boxes, size_t slot_bytes,
+                                                               const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
+                                                               uint32_t* d_ok, uint32_t* d_status, void* stream) {
+    if (!r || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (r->job_acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update_dev");
+    if (rows == 0) return SDA_OK;
+    SDA_TRY(job_claim(r, first_pos, rows, false));
+    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    const SboxState* d_states = nullptr;
+    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, r->ctx.device, s,
+                                       &d_states));
+    if (r->additive) {
+        int waves = 0;
+        HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, r->job_row_len,
+                                             r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), d_status, s, &waves));
+        note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
+    } else {
+        HIP_TRY(launch_sealed_stream_weighted(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, r->job_row_len, first_pos,
+                                              r->job(), r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), d_status, s));
+        note_kernel("sbox_poly_kernel + sealed_stream_weighted_kernel<8, %s>", r->k <= 16 ? "lds" : "global");
+    }
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);     // the whole call, not only its last launch
+    return job_claim(r, first_pos, rows, true);
+}
+
+extern "C" int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r, int64_t* d_out, size_t out_cap, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
+    if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(r->ctx.use());
+    // the padding of the last batch is summed like every output and not written (batched.rs:94)
+    if (r->job_out) SDA_TRY(acc_finish(r->job_acc, r->job_out, r->mod, d_out, r->ctx.pick(stream)));
+    r->job_begun = false;
     return SDA_OK;
 }
 

@@ -877,6 +877,26 @@ struct XSalsaBytes {
     }
 };
 
+// Row r of a sealed job, for the wave that streams it: true = `rs` is open on the row's ciphertext.  A box the verify pass refused
+// (tag, length, all-zero shared secret) carries `bad`; the length is tested again here so that the row can never leave its slot
+// whatever the state says.  The other refusals are the verdicts of stream_row_range on the plaintext this row would have been
+// opened to.
+__device__ __forceinline__ bool sealed_row_open(RowStreamT<XSalsaBytes>& rs, const uint8_t* __restrict__ boxes, uint64_t slot,
+                                                const uint64_t* __restrict__ row_bytes, uint64_t max_box,
+                                                const SboxState* __restrict__ states, uint64_t r, uint64_t len,
+                                                uint32_t* __restrict__ status, uint8_t* tile, uint32_t* kstream) {
+    const bool lead = (threadIdx.x & 63) == 0;
+    const uint64_t have = row_bytes[r];
+    if (!(have >= 48 && have <= max_box && have <= slot && !states[r].bad)) return false;
+    const uint64_t a = r * slot + 48, b = r * slot + have;
+    if (len == 0) { if (a != b && lead) atomicOr(status, SDA_VARINT_ROW_COUNT); return false; }
+    if (a == b) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); return false; }
+    rs.crypt.open(states[r], kstream);
+    if (rs.crypt.byte_at(boxes[b - 1], b - 1 - a) & 0x80u) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); return false; }
+    rs.open(boxes, a, b, len, tile);
+    return true;
+}
+
 template <int kCombWaves>
 __global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_combine_kernel(
     const uint8_t* __restrict__ boxes, uint64_t slot, const uint64_t* __restrict__ row_bytes, uint64_t max_box,
@@ -891,23 +911,7 @@ __global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_combine_kernel(
     const uint64_t r = (uint64_t)blockIdx.x * kCombWaves + wave;
     for (int i = threadIdx.x; i < kCombWindow; i += kCombWaves * 64) { lo32[i] = 0; hi32[i] = 0; }
     RowStreamT<XSalsaBytes> rs;
-    bool live = false;
-    if (r < rows) {
-        const uint64_t have = row_bytes[r];
-        // a box the verify pass refused (tag, length, all-zero shared secret) carries `bad`; the length is tested again here
-        // so that the row can never leave its slot whatever the state says
-        if (have >= 48 && have <= max_box && have <= slot && !states[r].bad) {
-            const uint64_t a = r * slot + 48, b = r * slot + have;
-            // the verdicts of stream_row_range on the plaintext this row would have been opened to
-            if (len == 0) { if (a != b && lead) atomicOr(status, SDA_VARINT_ROW_COUNT); }
-            else if (a == b) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); }
-            else {
-                rs.crypt.open(states[r], kstream[wave]);
-                if (rs.crypt.byte_at(boxes[b - 1], b - 1 - a) & 0x80u) { if (lead) atomicOr(status, SDA_VARINT_UNTERMINATED); }
-                else { live = true; rs.open(boxes, a, b, len, tiles[wave]); }
-            }
-        }
-    }
+    bool live = r < rows && sealed_row_open(rs, boxes, slot, row_bytes, max_box, states, r, len, status, tiles[wave], kstream[wave]);
     WindowSink sink{lo32, hi32, 0, acc_lo, acc_hi};
     __syncthreads();
     for (;;) {
@@ -919,6 +923,112 @@ __global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_combine_kernel(
         __syncthreads();
         if (window_flush<kCombWaves>(lo32, hi32, sink, cols, len)) break;
     }
+}
+
+// ---- sealed clerking results -> secrets (receive.rs:120-146: decrypt every clerking result, then reconstruct) ------------------
+// Packed reconstruction is a fixed k x n' matrix R per clerk-index set, so secret[b k + s] = sum over rows i of
+// R[s][i] * share_i[b] mod q: a WEIGHTED clerk sum, and a row can be folded in on its own, in any order, once its coefficient
+// column is known.  The sealed kernel above with a Montgomery multiply between the decoder and the window: the sink reduces a
+// value (any int64) to its canonical residue, multiplies it by the k coefficients of the row's position (Montgomery form, so
+// the REDC of the product is the canonical R[s][i] * v mod q, below 2^62) and adds the k products to the outputs b k + s.  The
+// window slides over OUTPUT columns; a product beyond it goes to the global 128-bit accumulator directly, so the sums are exact
+// however far rows drift apart, and at most 65535 rows of products below 2^63 cannot overflow them.  The fold mod q happens
+// once, at finish.  With k = 100 a 4 KiB group of a row spans far more outputs than the window holds: most products of such a
+// shape take the direct path.
+//
+// The coefficients of position i are row i of the transposed matrix Rt [n'][k], contiguous.  k <= kCoefLds: the wave keeps its k
+// coefficients in LDS.  Larger k (the shipped PSS_155 shapes have k = 100): read from Rt, the address is wave-uniform.
+// LDS of the 8-wave instance: 8.3 KB of stream tiles + 33 KB of keystream tiles + 32 KB of window + 1 KB of coefficients =
+// 75 KB, two workgroups in the 160 KB of a CU (the 16-wave form would leave room for one; it is not instantiated).
+// One wave streams one row: a reveal of few, long rows has little parallelism.
+static constexpr int kCoefLds = 16;
+
+struct WeightedSink {
+    WindowSink win;                   // over output columns b k + s
+    const uint64_t* coef;             // the k coefficients of this wave's row
+    uint32_t k;
+    uint64_t batches, m, mu, pinv;
+    __device__ __forceinline__ void operator()(uint64_t b, int64_t v) const {
+        if (b >= batches) return;     // past ceil(dimension / k): decoded for validity, otherwise ignored
+        const uint64_t x = canon_i64(v, m, mu);
+        const uint64_t c = b * k;
+        for (uint32_t s = 0; s < k; ++s) win(c + s, (int64_t)mont_redc(mul64x64(coef[s], x), m, pinv));
+    }
+};
+
+template <int kCombWaves, bool kLds>
+__global__ __launch_bounds__(kCombWaves * 64) void sealed_stream_weighted_kernel(
+    const uint8_t* __restrict__ boxes, uint64_t slot, const uint64_t* __restrict__ row_bytes, uint64_t max_box,
+    const SboxState* __restrict__ states, uint64_t rows, uint64_t len, uint64_t first_pos, WeightedJob J,
+    uint64_t* __restrict__ acc_lo, int64_t* __restrict__ acc_hi, uint32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kCombWaves][kStreamTile];
+    __shared__ uint32_t kstream[kCombWaves][kKsTile];
+    __shared__ unsigned long long lo32[kCombWindow], hi32[kCombWindow];
+    __shared__ uint64_t cols[kCombWaves];
+    __shared__ uint32_t alive[kCombWaves];
+    __shared__ uint64_t coefs[kLds ? kCombWaves : 1][kCoefLds];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const bool lead = lane == 0;
+    const uint64_t r = (uint64_t)blockIdx.x * kCombWaves + wave;
+    const uint64_t total = J.batches * J.k;                      // outputs = accumulators (the last batch is padded)
+    for (int i = threadIdx.x; i < kCombWindow; i += kCombWaves * 64) { lo32[i] = 0; hi32[i] = 0; }
+    const uint64_t* coef = J.Rt + (first_pos + (r < rows ? r : 0)) * J.k;
+    if (kLds) {
+        if (r < rows && (uint32_t)lane < J.k) coefs[wave][lane] = coef[lane];
+        coef = coefs[wave];
+    }
+    RowStreamT<XSalsaBytes> rs;
+    bool live = r < rows && sealed_row_open(rs, boxes, slot, row_bytes, max_box, states, r, len, status, tiles[wave], kstream[wave]);
+    WeightedSink sink{{lo32, hi32, 0, acc_lo, acc_hi}, coef, J.k, J.batches, J.m, J.mu, J.pinv};
+    __syncthreads();
+    for (;;) {
+        if (live) {
+            rs.next_group(sink);
+            if (rs.done()) { rs.close(status); live = false; }
+        }
+        if (lead) {
+            // a row past its last batch no longer holds the window, but is streamed to its end: the surplus is validated
+            cols[wave] = live && rs.col < J.batches ? rs.col * J.k : total;
+            alive[wave] = live;
+        }
+        __syncthreads();
+        uint32_t any = 0;
+#pragma unroll
+        for (int w = 0; w < kCombWaves; ++w) any |= alive[w];
+        const bool flushed = window_flush<kCombWaves>(lo32, hi32, sink.win, cols, total);   // ends on a barrier: alive[] is read
+        if (flushed && !any) break;
+    }
+}
+
+// The plaintext-row sibling: rows already decoded, [rows][row_stride] int64.  One lane per batch, the rows of the call in a loop:
+// the un-reduced 128-bit dot product of packed_reconstruct_kernel over THIS call's rows, one REDC, one add to the accumulators.
+__global__ __launch_bounds__(kVT) void weighted_rows_kernel(const int64_t* __restrict__ shares, uint64_t row_stride, uint32_t rows,
+                                                            uint64_t first_pos, WeightedJob J, uint64_t* __restrict__ acc_lo,
+                                                            int64_t* __restrict__ acc_hi, uint32_t e_per_group) {
+    const uint64_t b = (uint64_t)blockIdx.x * kVT + threadIdx.x;
+    if (b >= J.batches) return;
+    const uint32_t e0 = blockIdx.y * e_per_group, e1 = e0 + e_per_group < J.k ? e0 + e_per_group : J.k;
+    for (uint32_t e = e0; e < e1; ++e) {
+        U128 acc{0, 0};
+        uint32_t since = 0;
+        for (uint32_t c = 0; c < rows; ++c) {
+            const uint64_t v = canon_i64(shares[(uint64_t)c * row_stride + b], J.m, J.mu);
+            mac128(acc, J.Rt[(first_pos + c) * J.k + e], v);
+            if (++since == 4) { mont_acc_condsub(acc, J.m); since = 0; }
+        }
+        mont_acc_condsub(acc, J.m);
+        const uint64_t o = b * J.k + e;
+        acc_atomic_add(acc_lo + o, acc_hi + o, mont_redc(acc, J.m, J.pinv), 0);
+    }
+}
+
+// R [k][n] -> Rt [n][k]
+__global__ __launch_bounds__(kVT) void transpose_u64_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t k,
+                                                            uint32_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kVT + threadIdx.x;
+    if (i >= (uint64_t)k * n) return;
+    const uint64_t pos = i / k, s = i - pos * k;
+    out[i] = in[s * n + pos];
 }
 
 // ---- share rows -> sealed boxes without the wire buffer (participate.rs:82-101: encode_var every share, then seal) --------
@@ -1092,6 +1202,45 @@ hipError_t launch_sealed_stream_combine(const uint8_t* d_boxes, size_t slot, con
     else
         sealed_stream_combine_kernel<8><<<dim3((unsigned)groups), dim3(8 * 64), 0, s>>>(d_boxes, slot, d_row_bytes, max_box_bytes, d_states,
                                                                                      rows, len, d_acc_lo, d_acc_hi, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_sealed_stream_weighted(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows,
+                                         size_t max_box_bytes, const SboxState* d_states, size_t len, size_t first_pos,
+                                         const WeightedJob& J, uint64_t* d_acc_lo, int64_t* d_acc_hi, uint32_t* d_status,
+                                         hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const uint64_t groups = vceil(rows, 8);
+    if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (J.k <= (uint32_t)kCoefLds)
+        sealed_stream_weighted_kernel<8, true><<<dim3((unsigned)groups), dim3(8 * 64), 0, s>>>(
+            d_boxes, slot, d_row_bytes, max_box_bytes, d_states, rows, len, first_pos, J, d_acc_lo, d_acc_hi, d_status);
+    else
+        sealed_stream_weighted_kernel<8, false><<<dim3((unsigned)groups), dim3(8 * 64), 0, s>>>(
+            d_boxes, slot, d_row_bytes, max_box_bytes, d_states, rows, len, first_pos, J, d_acc_lo, d_acc_hi, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_weighted_rows(const int64_t* d_shares, size_t row_stride, size_t rows, size_t first_pos, const WeightedJob& J,
+                                uint64_t* d_acc_lo, int64_t* d_acc_hi, hipStream_t s) {
+    if (rows == 0 || J.batches == 0) return hipSuccess;
+    const uint64_t blocks = vceil(J.batches, kVT);
+    if (blocks > 0x7FFFFFFFull || rows > 0xFFFFFFFFull) return hipErrorInvalidConfiguration;
+    // as launch_packed_reconstruct: the k secrets of a batch are split into groups when the batches alone do not fill the chip
+    uint64_t groups = blocks < 2048 ? vceil(2048, blocks) : 1;
+    if (groups > J.k) groups = J.k;
+    const uint32_t e_per_group = (uint32_t)vceil(J.k, groups);
+    groups = vceil(J.k, e_per_group);
+    weighted_rows_kernel<<<dim3((unsigned)blocks, (unsigned)groups), dim3(kVT), 0, s>>>(d_shares, row_stride, (uint32_t)rows, first_pos, J,
+                                                                                      d_acc_lo, d_acc_hi, e_per_group);
+    return hipGetLastError();
+}
+
+hipError_t launch_transpose_u64(const uint64_t* d_in, uint64_t* d_out, uint32_t k, uint32_t n, hipStream_t s) {
+    const uint64_t blocks = vceil((uint64_t)k * n, kVT);
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    transpose_u64_kernel<<<dim3((unsigned)blocks), dim3(kVT), 0, s>>>(d_in, d_out, k, n);
     return hipGetLastError();
 }
 

@@ -303,6 +303,25 @@ struct SecretReconstructor {
         out.resize(n_out);
         return out;
     }
+    // the same as a streaming job on device-resident rows (receive.rs:120-146); no update synchronises the stream.  indices[i] is
+    // the clerk index of position i (Additive: may be empty); a position is fed once, in any order, by either update form
+    void begin_dev(const std::vector<size_t>& indices, size_t n_rows, size_t row_len, void* stream = nullptr) {
+        if (!indices.empty() && indices.size() != n_rows) detail::check(SDA_ERR_INVALID_ARGUMENT);
+        detail::check(sda_secret_reconstructor_begin_dev(h, indices.empty() ? nullptr : indices.data(), n_rows, row_len, stream));
+    }
+    void update_dev(size_t first_pos, const int64_t* d_shares, size_t rows, size_t row_stride, void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_update_dev(h, first_pos, d_shares, rows, row_stride, stream));
+    }
+    // clerking results that are still sealed boxes, laid out as for sda_sealedbox_open_rows_dev; *d_status != 0: do not use the result
+    void update_sealed_rows_dev(ShareCodec& codec, SealedBox& box, const EncryptionKey& pk, const DecryptionKey& sk, size_t first_pos,
+                                const uint8_t* d_boxes, size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows,
+                                size_t max_box_bytes, uint32_t* d_status, uint32_t* d_ok = nullptr, void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_update_sealed_rows_dev(h, codec.h, box.h, pk.data(), sk.data(), first_pos, d_boxes, slot_bytes,
+                                                                      d_row_bytes, rows, max_box_bytes, d_ok, d_status, stream));
+    }
+    void finish_dev(int64_t* d_out, size_t out_cap, void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_finish_dev(h, d_out, out_cap, stream));
+    }
 };
 
 // ---- masking traits -----------------------------------------------------------------------------
