@@ -60,8 +60,11 @@ int  sda_debug_env_knobs_compiled_in(void);              /* 1 only in an SDA_AB_
 const char* sda_debug_last_kernel(void);
 /* The kernel-selection table without a device or a handle (sda_amd/csrc/path_select.hpp: the ONE place the decision is made):
  * `knobs` = comma-separated selection knob names from the list above (NULL or "" = defaults; the process-wide knob state is not
- * read).  Writes "wide=... narrow=... r_bits=... call20=... call12=... injected=... fused20=... fused12=... transform_shape=.
- * eight_term_ok=." (family names: additive n31 ngemm l31 mont64 l31_global fft mfma generic). */
+ * read; SDA_NO_LAZY and SDA_FFT_G, the per-handle knobs of the transform kernel's plan, are taken too, the latter with its value:
+ * "SDA_FFT_G=4").  Writes "wide=... narrow=... r_bits=... call20=... call12=... injected=... fused20=... fused12=... transform_shape=.
+ * eight_term_ok=. l31_radix=.. l31_group=. transform_narrow=. transform_lazy=. transform_g=.. transform_tw_lds=." (family names:
+ * additive n31 ngemm l31 mont64 l31_global fft mfma generic; the transform_* fields are the plan of packed_gen_fft_kernel - 32-bit
+ * values, lazy radix-3 levels, batches per workgroup, twiddle tables in LDS - and 0 where another wide family serves). */
 /* streams and memory figures for the tests, so that they need no second HIP binding in their process (a Python process that
  * loads this library and then PyTorch ends up with two HIP runtimes): non-blocking streams, hipMemGetInfo */
 int  sda_debug_stream_create(void** stream);

@@ -870,6 +870,9 @@ static int l31_params(uint64_t p, L31Params& lp) {
 // (SURVEY.md App. B); the kernel also needs the group's values in LDS (p < 2^62 holds for every modulus the library takes).
 // Two workgroups per CU (80 KB each) when a group of 8 batches fits, with the twiddle tables in LDS too if there is room.
 static bool fft_narrow(uint64_t p, const PathKnobs& kn) { return p < (1ull << 30) && !kn.no_narrow; }   // 4p < 2^32: the kernel's lazy ranges in 32 bits
+// the narrow kernel's lazy radix-3 levels (f_r3<true>, fft_kernels.hip): every one of the b levels lets the A chain grow by 4p and the
+// last Shoup product takes any 32-bit operand, so (4b + 4) p < 2^32 admits it (tests/test_narrow_model.py, tests/transform_limits.py)
+static bool fft_lazy(bool narrow, uint32_t b, uint64_t p, bool no_lazy) { return narrow && (4ull * b + 4) * p < (1ull << 32) && !no_lazy; }
 static bool fft_shape(const sda_share_generator* g, const PathKnobs& kn, uint32_t& a, uint32_t& b, uint32_t& G, uint32_t& tw_lds) {
     const bool narrow = fft_narrow(g->mod.m, kn);
     const uint64_t p = g->mod.m, m2 = (uint64_t)g->k + g->t + 1, m3 = (uint64_t)g->n + 1;
@@ -972,7 +975,7 @@ static int build_fft(sda_share_generator* g, uint32_t a, uint32_t b, uint32_t G,
     shoup_pair(m2i, p, F.scale, F.scale_s);
     if (narrow) { F.omega_s = (F.omega << 32) / p; F.scale_s = (F.scale << 32) / p; }
     F.one_s = narrow ? (1ull << 32) / p : 0;
-    F.lazy = narrow && (4ull * b + 4) * p < (1ull << 32) && !g->knob_no_lazy ? 1u : 0u;
+    F.lazy = fft_lazy(narrow, b, p, g->knob_no_lazy != 0) ? 1u : 0u;
     F.magic_k1 = (uint32_t)(0x100000000ull / ((uint64_t)g->k + 1)) + 1u;                 // k + 1 >= 2
     F.magic_t = g->t > 1 ? (uint32_t)(0x100000000ull / g->t) + 1u : 0u;
     F.want_threads = (uint32_t)knob(KNOB_FFT_THREADS);
@@ -1133,7 +1136,9 @@ extern "C" int sda_share_generator_new(const sda_sharing_scheme_t* scheme, sda_s
 #ifdef SDA_TEST_HOOKS
 // The decision table without a device (tests/test_path_select.py runs it on a machine with no GPU): validates the scheme, builds
 // the host-side facts, calls select_path() under the NAMED knobs (comma separated, NULL / "" = defaults; the process-wide knob
-// state is not read) and describes the choice and what each kind of call would run.
+// state is not read) and describes the choice and what each kind of call would run.  The transform kernel's plan (fft_shape, fft_lazy:
+// value width, lazy levels, batches per workgroup, twiddles in LDS) follows the per-handle knobs too: SDA_NO_LAZY, and SDA_FFT_G with
+// its value as "SDA_FFT_G=4".
 extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const char* knobs, char* out, size_t cap) {
     if (!out || cap < 8) return fail(SDA_ERR_INVALID_ARGUMENT, "out needs a buffer");
     out[0] = 0;
@@ -1141,6 +1146,8 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
     if (sharing_is_additive(scheme)) { snprintf(out, cap, "wide=additive narrow=none call20=additive fused20=additive"); return SDA_OK; }
     SDA_TRY(validate_packed(*scheme));
     PathKnobs kn;
+    long fft_g = 0;
+    bool no_lazy = false;
     for (const char* q = knobs ? knobs : ""; *q;) {
         const char* e = strchr(q, ',');
         const size_t len = e ? (size_t)(e - q) : strlen(q);
@@ -1152,6 +1159,8 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
         else if (name == "SDA_NO_MFMA") kn.no_mfma = true;
         else if (name == "SDA_NO_NARROW") kn.no_narrow = true;
         else if (name == "SDA_NO_NGEMM") kn.no_ngemm = true;
+        else if (name == "SDA_NO_LAZY") no_lazy = true;
+        else if (name.compare(0, 10, "SDA_FFT_G=") == 0) fft_g = strtol(name.c_str() + 10, nullptr, 10);
         else if (!name.empty()) return fail(SDA_ERR_INVALID_ARGUMENT, "%s is not a selection knob", name.c_str());
         q += len + (e ? 1 : 0);
     }
@@ -1159,6 +1168,7 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
     if (!g) return fail(SDA_ERR_ALLOC, "out of memory");
     g->scheme = *scheme; g->additive = false;
     g->n = (uint32_t)scheme->share_count; g->k = (uint32_t)scheme->secret_count; g->t = (uint32_t)scheme->privacy_threshold;
+    g->knob_fft_g = fft_g; g->knob_no_lazy = no_lazy ? 1 : 0;
     int st = make_mod(scheme->modulus, g->mod);
     if (st == SDA_OK) st = build_packed_share_matrix(*scheme, g->mod.m, g->Mmont);
     if (st == SDA_OK) {
@@ -1172,13 +1182,17 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
             const bool sys = build_systematic_share_matrix(g->scheme, g->mod.m, g->Msys);
             l31_group = l31_group_mode(g->Mmont, sys ? &g->Msys : nullptr, g->k + g->t, g->mod.m, false, false);
         }
+        // the transform kernel's plan, from the functions sda_share_generator_new() builds it with (zeros where another family serves)
+        uint32_t fa = 0, fb = 0, fG = 0, ftw = 0;
+        const bool fft = c.wide == WIDE_FFT && fft_shape(g, kn, fa, fb, fG, ftw);
+        const bool fnarrow = fft && fft_narrow(g->mod.m, kn);
         snprintf(out, cap, "wide=%s narrow=%s r_bits=%u call20=%s call12=%s injected=%s fused20=%s fused12=%s transform_shape=%d eight_term_ok=%d "
-                 "l31_radix=%u l31_group=%u",
+                 "l31_radix=%u l31_group=%u transform_narrow=%d transform_lazy=%d transform_g=%u transform_tw_lds=%u",
                  wide_name(c.wide), narrow_name(c.narrow), c.wide == WIDE_L31 ? c.l31_r_bits : 0u, family_name(path_for_call(c, false, 20)),
                  family_name(path_for_call(c, false, 12)), family_name(path_for_call(c, true, 20)),
                  fused_for_call(c, 20) == FAM_GENERIC ? "none" : family_name(fused_for_call(c, 20)),
                  fused_for_call(c, 12) == FAM_GENERIC ? "none" : family_name(fused_for_call(c, 12)), (int)f.transform_shape, (int)f.eight_term_ok,
-                 l31_radix, (unsigned)l31_group);
+                 l31_radix, (unsigned)l31_group, (int)fnarrow, (int)(fft && fft_lazy(fnarrow, fb, g->mod.m, no_lazy)), fft ? fG : 0u, fft ? ftw : 0u);
     }
     sda_share_generator_free(g);
     return st;

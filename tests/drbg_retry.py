@@ -298,9 +298,9 @@ DUAL_CASES = [
 # needs (fft_shape, sda_capi.cpp): 8 for the wide (40, 23, 242) and (100, 155, 728), 4 for (100, 155, 2186) - three batches are one
 # workgroup at off = 0 - and 1 for (100, 155, 19682), off = 0 .. 2.  The non-zero offsets of G = 4 and G = 2 and off = 3 .. 7 of
 # G = 1 come from the knob SDA_FFT_G alone (snapshotted when the generator is created, so _knobs() runs first).  NOT OBSERVABLE
-# from here: neither sda_debug_last_kernel() nor sda_debug_select_path() reports G, so a knob that was ignored would leave the
-# G4 / G2 / G1 cases passing on the G = 8 branch; a field of sda_debug_select_path that reports G would close that and is left
-# for a change to the library.
+# on the device: sda_debug_last_kernel() does not report G, so a knob that was ignored would leave the G4 / G2 / G1 cases passing
+# on the G = 8 branch.  On the host sda_debug_select_path reports the plan ("SDA_FFT_G=4" -> transform_g=4);
+# tests/test_transform_limits_reach.py pins it for every group form.
 _F8, _F242 = WIDE_PRIMES["fft8"][0], WIDE_PRIMES["fft242"][0]
 FFT_CASES = [
     _case("fft-1-6-8", "packed_gen_fft_kernel<20, ", 1, 6, 8, _F8, 9, knobs=["SDA_FORCE_FFT"], odd=True),

@@ -109,13 +109,16 @@ def test_narrow_matrix_kernels_vs_oracle_and_wide(gpu, p, k, t, n, dim):
     (TSS_P2, 100, 155, 19682, 4318906, 1814687, 250),                 # tss's PSS_155_19682_100 (one batch per workgroup)
     (TSS_P1, 40, 23, 242, None, None, 40 * 40),                       # 64 / 243 points
     (P29, 7, 8, 26, None, None, 7 * 100 + 3),                         # forced below: small tss-valid shape, 29-bit prime
-    (P30, 3, 4, 8, None, None, 3 * 50)])                              # 2^30 <= p: stays on the 64-bit transform kernel
+    (P30, 3, 4, 8, None, None, 3 * 50)])                              # p < 2^30 but 12 p >= 2^32: the 32-bit kernel without lazy levels
 def test_narrow_transform_kernel_vs_oracle_and_wide(gpu, p, k, t, n, w2, w3, dim):
-    from sda_amd import crypto
+    from sda_amd import capi, crypto
     from sda_amd.device import DeviceBuffer
     from oracle import coracle
     w2 = w2 or _root(p, k + t + 1)
     w3 = w3 or _root(p, n + 1)
+    b = len(np.base_repr(n + 1, 3)) - 1                                     # n + 1 = 3^b
+    lazy_fits = (4 * b + 4) * p < (1 << 32)                                 # tss's primes; not P29 (16 p) nor P30 (12 p)
+    suffix = {True: "unsigned int, true>" if lazy_fits else "unsigned int, false>", "no_lazy": "unsigned int, false>", False: "unsigned long, false>"}
     rng = np.random.default_rng(k + n)
     secrets = rng.integers(-(1 << 62), 1 << 62, size=dim, dtype=np.int64)
     sec2 = rng.integers(0, p, size=(2, dim), dtype=np.int64)
@@ -133,11 +136,13 @@ def test_narrow_transform_kernel_vs_oracle_and_wide(gpu, p, k, t, n, w2, w3, dim
         rand = np.random.default_rng(7).integers(-(1 << 62), 1 << 62, size=B * t, dtype=np.int64)
         got = gen.generate(secrets, rand)
         assert np.array_equal(got, coracle.packed_generate(p, k, t, n, w2, w3, secrets, rand)), narrow
+        assert capi.load().sda_debug_last_kernel().decode().endswith(suffix[narrow]), (narrow, capi.load().sda_debug_last_kernel())
         gen.set_drbg_key(KEY)
         d_sec = DeviceBuffer.from_numpy(sec2)
         Bs = B + (B & 1)
         d_out = DeviceBuffer(2 * n * Bs).zero()
         gen.generate_batch_dev(d_sec.ptr, 2, dim, dim, d_out.ptr, n * Bs, Bs, first_participant=70)
+        assert capi.load().sda_debug_last_kernel().decode().endswith(suffix[narrow]), (narrow, capi.load().sda_debug_last_kernel())
         o = d_out.to_numpy().reshape(2, n, Bs)
         for q in range(2):
             w = coracle.packed_generate(p, k, t, n, w2, w3, sec2[q], coracle.drbg_fill(KEY, 70 + q, B, t, p))
