@@ -702,6 +702,30 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   handle and the codec on different devices.  Ephemeral secrets are uploaded, used and wiped as in
  *                   seal_rows_dev.  Uses the sealed-box handle's scratch: the one-stream-at-a-time rule holds.
  *
+ *   sda_share_generator_generate_sealed_rows_dev : participate.rs:75-101 in one call - the secrets of `participants` participants
+ *                   in, the sealed rows of all n = share_count clerking jobs out; no share is written to device memory and the
+ *                   call needs no share buffer.  pks holds the n clerk keys in clerk order.  Row r = c * participants + p is the
+ *                   box of clerk c for participant p, at d_boxes + r * slot_bytes with its length in d_row_bytes[r]: job-major,
+ *                   so clerk c's slice (d_boxes + c * participants * slot_bytes, d_row_bytes + c * participants) is the
+ *                   (d_boxes, slot_bytes, d_row_bytes) argument of sda_share_combiner_update_sealed_rows_dev.  Every box is byte
+ *                   for byte what sda_share_generator_generate_batch_dev (d_rand = NULL, out_stride_clerk = participants * B,
+ *                   out_stride_participant = B, B = batches) followed by sda_sealedbox_seal_share_rows_dev (n_pks = n,
+ *                   rows_per_key = participants) gives under the same CSPRNG key, stream ids first_participant + p, share map
+ *                   (sda_share_generator_csprng_share_map), round count and ephemeral secrets (esk: NULL = OS entropy, else
+ *                   participants * n * 32 bytes, row r's secret at 32 r, TESTS ONLY).  In production mode the call runs under a
+ *                   call key of its own, like generate_batch_dev.  The wave that encodes and encrypts a row computes the row's
+ *                   shares itself, from the secrets and the sda-drbg-v1 draws of its batches: every clerk's wave derives those
+ *                   draws again (up to n times the ChaCha work of generate_batch_dev).  LIMITS: the device CSPRNG only (no
+ *                   injected randomness), canonical values only (SDA_VALUES_RUST_SIGNED: SDA_ERR_UNSUPPORTED), additive sharing
+ *                   or packed Shamir with secret_count + privacy_threshold <= 32 (larger: SDA_ERR_UNSUPPORTED - call
+ *                   generate_batch_dev + seal_share_rows_dev).  SDA_ERR_INVALID_ARGUMENT before any launch for: a NULL handle or
+ *                   pointer (d_secrets may be NULL only when len == 0), secrets_stride < len, slot_bytes not a multiple of 16
+ *                   or below sda_varint_slot_size(B) + 48, d_boxes not 16-byte aligned, the three handles not on one device,
+ *                   stream ids at or above 2^56.  participants == 0 returns SDA_OK; len == 0 gives n * participants boxes of the
+ *                   empty message.  A clerk key of small order refuses that clerk's rows only (length 0, the epk written), the
+ *                   other clerks' rows are intact.  Ephemeral secrets are uploaded, used and wiped as in seal_rows_dev.  Uses the
+ *                   sealed-box handle's scratch: the one-stream-at-a-time rule holds.
+ *
  *   sda_mask_combiner_update_sealed_rows_dev : receive.rs:101-118 from the participants' sealed mask encryptions - an update
  *                   form of the mask combiner's device job (sda_mask_combiner_begin_dev above), rows laid out as for
  *                   open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does (d_ok[r] when d_ok is given;
@@ -759,6 +783,12 @@ int  sda_sealedbox_seal_share_rows_dev(sda_sealedbox_t* b, sda_varint_codec_t* c
                                        size_t rows_per_key, const uint8_t* esk /* NULL = OS entropy; else rows*32, tests only */,
                                        const int64_t* d_values, size_t rows, size_t len, size_t row_stride, uint8_t* d_boxes,
                                        size_t slot_bytes, uint64_t* d_row_bytes, void* stream);
+int  sda_share_generator_generate_sealed_rows_dev(sda_share_generator_t* g, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                  const uint8_t* pks /* share_count keys, 32 B each, in clerk order */,
+                                                  const uint8_t* esk /* NULL = OS entropy; else participants*share_count*32, tests only */,
+                                                  const int64_t* d_secrets, size_t participants, size_t len, size_t secrets_stride,
+                                                  uint64_t first_participant, uint8_t* d_boxes, size_t slot_bytes,
+                                                  uint64_t* d_row_bytes, void* stream);
 int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
                                                const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,

@@ -39,6 +39,8 @@
  *   SDA_NGEMM_CLERK_WG 1       limb GEMM, dual-role launch: the clerk sum in clerk WORKGROUPS at fixed grid positions (rounds 4 - 5) instead
  *                              of the clerk WAVES inside every share-generation workgroup (round 6, the default)
  *   SDA_SEALED_WAVES 16        sealed_stream_combine_kernel with 16 rows per workgroup (default, and the release library: always 8)
+ *   SDA_GENSEAL_BY_ROWS 1      share_seal_stream_kernel: a workgroup takes consecutive rows (participants of one clerk) instead of
+ *                              the clerks of one participant (default, and the release library)
  *   SDA_FORCE_COLLECTIVES 1    a one-rank communicator still goes through RCCL send/recv to itself
  * Built with -DSDA_AB_KNOBS (tools/build_ab_variant.sh; never by __graft_entry__.build()) an unset knob falls back to the
  * environment variable of the same name. */

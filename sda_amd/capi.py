@@ -198,6 +198,8 @@ SIGNATURES = {
     "sda_sealedbox_open": (C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, c_sizep]),
     "sda_sealedbox_seal_share_rows_dev": (C.c_int, [_H, _H, C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_void_p, C.c_size_t,
                                                     C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sda_share_generator_generate_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                               C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_share_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
                                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                             C.c_void_p]),

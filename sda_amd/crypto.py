@@ -231,6 +231,21 @@ class ShareGenerator(_Handle):
             self._h, d_secrets, participants, length, secrets_stride, d_rand or None, rand_stride,
             first_participant, d_out, out_stride_participant, out_stride_clerk, stream or None))
 
+    def generate_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", pks: Sequence[bytes], d_secrets: int, participants: int,
+                                 length: int, secrets_stride: int, d_boxes: int, slot_bytes: int, d_row_bytes: int,
+                                 first_participant: int = 0, esk: Optional[bytes] = None, stream: int = 0) -> None:
+        """secrets -> the sealed rows of every clerking job in one call (participate.rs:75-101); no share reaches device memory.
+        pks: the share_count clerk keys in clerk order.  Row c * participants + p = clerk c's box for participant p, at
+        d_boxes + row * slot_bytes, its length (0: refused) in d_row_bytes[row].  Device CSPRNG, canonical values, additive or
+        packed Shamir with secret_count + privacy_threshold <= 32."""
+        allpk = b"".join(pks)
+        assert len(allpk) == 32 * len(pks) and (esk is None or len(esk) == 32 * len(pks) * participants)
+        n = int(self._lib.sda_share_generator_share_count(self._h))
+        if len(pks) != n:
+            raise ValueError(f"one key per clerk: {n} keys, got {len(pks)}")
+        check(self._lib.sda_share_generator_generate_sealed_rows_dev(
+            self._h, codec._h, box._h, allpk, esk, d_secrets or None, participants, length, secrets_stride, first_participant,
+            d_boxes, slot_bytes, d_row_bytes, stream or None))
 
     def generate_combine_dev(self, combiner: "ShareCombiner", d_secrets: int, participants: int, length: int,
                              secrets_stride: int, d_out: int, out_stride_participant: int, out_stride_clerk: int,

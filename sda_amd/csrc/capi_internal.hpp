@@ -17,6 +17,10 @@ int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uin
 // pass (launch_varint_seal_stream), authenticate, wipe the ephemeral secrets - all on the handle's scratch
 int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key, const uint8_t* esk,
                                    const sda::VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
+// sda_share_generator_generate_sealed_rows_dev after its argument checks: the same sequence with the rows computed from the
+// secrets inside the encode pass (launch_share_seal_stream); n keys, rows_per_key = participants
+int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, const uint8_t* esk, const sda::ShareJob& J, int rounds,
+                                       uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
 int capi_sealedbox_device(const sda_sealedbox* b);
 
 // ---- path-selection knobs (A/B measurements and parity tests of the non-default kernels) -----------------------------------
@@ -28,7 +32,8 @@ enum Knob {
     KNOB_FORCE_GENERIC, KNOB_FORCE_MONT64, KNOB_FORCE_FFT, KNOB_FORCE_MFMA, KNOB_NO_MFMA, KNOB_NO_SIDE_STREAM,
     KNOB_SIDE_STREAM_WGS, KNOB_SIDE_STREAM_PRIORITY_HIGH, KNOB_FFT_G, KNOB_FFT_THREADS, KNOB_VARINT_PATH /* 1 stream, 2 scan */,
     KNOB_FORCE_COLLECTIVES, KNOB_NO_NARROW, KNOB_WIRE_WG_PER_CU, KNOB_SBOX_WG_PER_CU, KNOB_NO_LAZY, KNOB_NO_XCD_MAP, KNOB_NO_NGEMM, KNOB_NO_WIDE_GROUP, KNOB_NGEMM_CLERK_WG, KNOB_NO_KARATSUBA,
-    KNOB_SEALED_WAVES /* 16: the wide instance */, KNOB_COUNT
+    KNOB_SEALED_WAVES /* 16: the wide instance */, KNOB_GENSEAL_BY_ROWS /* share_seal_stream_kernel: consecutive rows per workgroup */,
+    KNOB_COUNT
 };
 long knob(Knob k);             // 0 = unset / default
 // an UNUSED dynamic-LDS request that caps the resident workgroups of a launch at wg_per_cu per CU (0: no cap), so that a

@@ -373,6 +373,24 @@ hipError_t launch_transpose_u64(const uint64_t* d_in, uint64_t* d_out, uint32_t 
 // a row whose state says `bad` is left alone (length 0)
 hipError_t launch_varint_seal_stream(const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
                                      uint64_t* d_msg_bytes, hipStream_t s);
+// secrets -> the ciphertext of a participation's sealed boxes in one pass: the shares of row r = c * participants + p (clerk c,
+// participant p) are computed by the wave that encodes and encrypts them (sda-drbg-v1 draws, stream first_participant + p) and
+// never reach memory.  States, box layout and d_msg_bytes as launch_varint_seal_stream
+struct ShareJob {
+    const int64_t* secrets;  size_t secrets_stride;   // participant p at secrets + p * secrets_stride
+    size_t len, participants;                         // secrets per participant
+    uint64_t batches;                                 // values per row: ceil(len / k)
+    uint64_t first_participant;
+    uint32_t n, k, t;                                 // additive: k = 1, t = n - 1
+    uint32_t additive;
+    uint32_t direct_rows;                             // packed: clerks 0 .. direct_rows - 1 receive the draws themselves (0 or t)
+    const uint64_t* M;                                // packed, device: (n - direct_rows) x (k + t), Montgomery form
+    ModParams mod;
+    MontParams mont;
+    DrbgKey key;
+};
+hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                    uint64_t* d_msg_bytes, hipStream_t s);
 hipError_t launch_varint_rowcheck(const uint8_t* d_bytes, size_t n_bytes, const uint64_t* d_offsets, size_t rows,
                                   size_t len, const uint64_t* d_block_val_off, uint32_t* d_status, hipStream_t s);
 

@@ -111,7 +111,7 @@ const char* const kKnobNames[sda::KNOB_COUNT] = {
     "SDA_FORCE_GENERIC", "SDA_FORCE_MONT64", "SDA_FORCE_FFT", "SDA_FORCE_MFMA", "SDA_NO_MFMA", "SDA_NO_SIDE_STREAM",
     "SDA_SIDE_STREAM_WGS", "SDA_SIDE_STREAM_PRIORITY", "SDA_FFT_G", "SDA_FFT_THREADS", "SDA_VARINT_PATH", "SDA_FORCE_COLLECTIVES",
     "SDA_NO_NARROW", "SDA_WIRE_WG_PER_CU", "SDA_SBOX_WG_PER_CU", "SDA_NO_LAZY", "SDA_NO_XCD_MAP", "SDA_NO_NGEMM", "SDA_NO_WIDE_GROUP", "SDA_NGEMM_CLERK_WG", "SDA_NO_KARATSUBA",
-    "SDA_SEALED_WAVES"};
+    "SDA_SEALED_WAVES", "SDA_GENSEAL_BY_ROWS"};
 std::atomic<long> g_knobs[sda::KNOB_COUNT];
 }  // namespace
 long sda::knob(sda::Knob k) {
@@ -635,6 +635,8 @@ struct sda_share_generator {
     Drbg drbg;
     Ctx ctx;
     DevBuf d_M, d_Msys, d_secrets, d_rand, d_out;
+    DevBuf d_Mseal;                      // generate_sealed_rows_dev: Mmont, then Msys, as built (Montgomery form), uploaded on first use
+    bool mseal_loaded = false;
     // generate_combine_dev for shapes without a dual-role kernel: the clerk sum of the previous tile runs on this side stream
     // beside the share generation (fork / join with events), created on first use
     bool rust_signed = false;            // SDA_VALUES_RUST_SIGNED (additive only): additive.rs:42-47 with Rust's own `%`
@@ -1202,7 +1204,7 @@ extern "C" int sda_debug_select_path(const sda_sharing_scheme_t* scheme, const c
 extern "C" void sda_share_generator_free(sda_share_generator_t* g) {
     if (!g) return;
     if (g->ctx.device >= 0) (void)hipSetDevice(g->ctx.device);
-    g->d_M.release(); g->d_Msys.release(); g->d_fft.release(); g->d_ngemm.release(); g->d_ngemm_sys.release(); g->d_cw_progress.release(); g->d_secrets.wipe_release(); g->d_rand.wipe_release(); g->d_out.wipe_release();
+    g->d_M.release(); g->d_Msys.release(); g->d_Mseal.release(); g->d_fft.release(); g->d_ngemm.release(); g->d_ngemm_sys.release(); g->d_cw_progress.release(); g->d_secrets.wipe_release(); g->d_rand.wipe_release(); g->d_out.wipe_release();
     if (g->aux) { (void)hipStreamSynchronize(g->aux); (void)hipStreamDestroy(g->aux); }
     if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
     if (g->ev_join) (void)hipEventDestroy(g->ev_join);
@@ -2818,6 +2820,60 @@ extern "C" int sda_sealedbox_seal_share_rows_dev(sda_sealedbox_t* b, sda_varint_
     SDA_TRY(capi_sealedbox_seal_share_rows(b, pks, n_pks, rows_per_key, esk, VarintRows{d_values, rows, len, row_stride}, d_boxes, slot_bytes,
                                            d_row_bytes, codec->ctx.pick(stream)));
     note_kernel("varint_seal_stream_kernel + sbox_poly_kernel");                    // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return SDA_OK;
+}
+
+// a participation from the secrets to its sealed clerking-job rows (participate.rs:75-101): setup, ONE pass that computes, encodes and
+// encrypts every clerk's shares, tags.  No share reaches memory and there is no share buffer.
+extern "C" int sda_share_generator_generate_sealed_rows_dev(sda_share_generator_t* g, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                            const uint8_t* pks, const uint8_t* esk, const int64_t* d_secrets,
+                                                            size_t participants, size_t len, size_t secrets_stride,
+                                                            uint64_t first_participant, uint8_t* d_boxes, size_t slot_bytes,
+                                                            uint64_t* d_row_bytes, void* stream) {
+    if (!g || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pks) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL clerk keys");
+    if (!d_boxes || !d_row_bytes || (len > 0 && !d_secrets)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (secrets_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "secrets_stride < len");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    const size_t B = (len + g->k - 1) / g->k;                     // values per row (additive: k = 1)
+    if (B > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(B) + SDA_SEALBYTES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(batches) + 48");
+    if (capi_sealedbox_device(b) != codec->ctx.device || g->ctx.device != codec->ctx.device)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the generator lives on device %d, the sealed-box handle on device %d, the codec on device %d",
+                    g->ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    if (g->rust_signed)
+        return fail(SDA_ERR_UNSUPPORTED, "the sealed form computes canonical shares only: SDA_VALUES_RUST_SIGNED takes generate_batch_dev + seal_share_rows_dev");
+    if (!g->additive && g->k + g->t > 32)
+        return fail(SDA_ERR_UNSUPPORTED, "the sealed form serves packed Shamir with secret_count + privacy_threshold <= 32 (this scheme: %u): "
+                                         "call generate_batch_dev + sda_sealedbox_seal_share_rows_dev", g->k + g->t);
+    size_t rows = 0;
+    if (__builtin_mul_overflow(participants, (size_t)g->n, &rows)) return fail(SDA_ERR_INVALID_ARGUMENT, "participants * share_count overflows");
+    if (participants == 0) return SDA_OK;
+    SDA_TRY(check_streams(first_participant, participants));
+    SDA_TRY(g->ctx.use());
+    const bool sys = effective_sys(g);
+    if (!g->additive && !g->mseal_loaded) {                       // both maps, back to back: the map is a per-call choice
+        SDA_TRY(g->d_Mseal.reserve((g->Mmont.size() + g->Msys.size()) * 8));
+        HIP_TRY(hipMemcpy(g->d_Mseal.p, g->Mmont.data(), g->Mmont.size() * 8, hipMemcpyHostToDevice));
+        if (!g->Msys.empty())
+            HIP_TRY(hipMemcpy(g->d_Mseal.as<uint64_t>() + g->Mmont.size(), g->Msys.data(), g->Msys.size() * 8, hipMemcpyHostToDevice));
+        g->mseal_loaded = true;
+    }
+    ShareJob J{};
+    J.secrets = d_secrets; J.secrets_stride = secrets_stride; J.len = len; J.participants = participants; J.batches = B;
+    J.first_participant = first_participant;
+    J.n = g->n; J.k = g->k; J.t = g->t; J.additive = g->additive ? 1u : 0u;
+    J.direct_rows = sys ? g->t : 0;
+    J.M = g->additive ? nullptr : g->d_Mseal.as<uint64_t>() + (sys ? g->Mmont.size() : 0);
+    J.mod = g->mod; J.mont = g->mont;
+    // like generate_batch_dev: nothing is drawn for an empty job, every other call runs under its own call key
+    if (len > 0) J.key = g->drbg.call_key();
+    g_last_gen_kernel[0] = 0;
+    const int st = capi_sealedbox_seal_generated_rows(b, pks, esk, J, g->drbg.rounds, d_boxes, slot_bytes, d_row_bytes, g->ctx.pick(stream));
+    explicit_bzero(&J.key, sizeof J.key);
+    if (st != SDA_OK) return st;
+    note_kernel("share_seal_stream_kernel<%d> + sbox_poly_kernel", g->drbg.rounds);      // the whole call, not only its last launch
     snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
     return SDA_OK;
 }

@@ -175,6 +175,26 @@ int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t 
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing share rows: launch failed: %s", hipGetErrorString(e));
 }
 
+// for sda_share_generator_generate_sealed_rows_dev (sda_capi.cpp), which has checked the arguments: as above, the encode pass
+// computing the rows it encodes
+int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, const uint8_t* esk, const ShareJob& J, int rounds,
+                                       uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
+    const size_t rows = (size_t)J.n * J.participants, max_msg = (size_t)J.batches * 10;
+    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
+    if (int st = scratch(b, rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
+    uint8_t *d_esk = nullptr, *d_pks = nullptr;
+    if (int st = stage_keys(b, pks, J.n, esk, rows, s, &d_esk, &d_pks)) return st;
+    SboxState* d_states = static_cast<SboxState*>(b->d_states);
+    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
+    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, J.n, J.participants, d_boxes, slot_bytes, rows, d_states, s);
+    if (e == hipSuccess) e = launch_share_seal_stream(J, rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    if (e == hipSuccess)
+        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing generated share rows: launch failed: %s", hipGetErrorString(e));
+}
+
 int capi_sealedbox_device(const sda_sealedbox* b) { return b->device; }
 
 // ---- host forms: one payload, staged through the device (what ShareEncryptor::encrypt / ShareDecryptor::decrypt call) ----

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "capi_internal.hpp"
+#include "drbg_quad.hpp"
 #include "kernels.hpp"
 #include "modarith.hpp"
 #include "sbox_primitives.hpp"
@@ -624,6 +625,32 @@ __device__ __forceinline__ void enc_load2(const int64_t* __restrict__ src, uint6
     }
 }
 
+// Where the encode loop's values come from.  Lane l of step j holds values 128 j + 2 l and 128 j + 2 l + 1; get(d, j, x, y) hands
+// them over (d = j % kStreamDepth, a compile-time constant after unrolling).  LoadValues: a row in global memory, one 16-byte
+// load per lane and step, kStreamDepth steps prefetched.
+struct LoadValues {
+    static constexpr int kDepth = kStreamDepth;
+    const int64_t* __restrict__ src;
+    uint64_t len;
+    bool vec;
+    int64_t wx[kStreamDepth], wy[kStreamDepth];
+    __device__ __forceinline__ void open(const int64_t* __restrict__ src_, uint64_t len_) {
+        const int lane = threadIdx.x & 63;
+        src = src_; len = len_;
+        vec = (((uintptr_t)src) & 15u) == 0;
+#pragma unroll
+        for (int d = 0; d < kStreamDepth; ++d) enc_load2(src, len, vec, (uint64_t)d * kEncVals + 2 * (uint64_t)lane, wx[d], wy[d]);
+    }
+    __device__ __forceinline__ void get(int d, uint64_t j, int64_t& x, int64_t& y) {
+        const int lane = threadIdx.x & 63;
+        x = wx[d]; y = wy[d];
+        asm volatile("" : "+v"(x), "+v"(y));
+        __builtin_amdgcn_sched_barrier(0);
+        enc_load2(src, len, vec, (j + kStreamDepth) * kEncVals + 2 * (uint64_t)lane, wx[d], wy[d]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+};
+
 // What the encode loop does to a 16-byte unit between the LDS tile and the global store.  Unit u of a row is its bytes
 // [16 u, 16 u + 16).  The rows of the plaintext kernel leave as they are:
 struct EncPlain {
@@ -633,36 +660,28 @@ struct EncPlain {
     __device__ __forceinline__ void apply(uint4&, uint64_t) const {}
 };
 
-// One wave encodes row r of R to dst (16-byte aligned) and stores its byte count in row_bytes[r].  Crypt: EncPlain, or the
+// One wave encodes the `len` values of `vals` as row r to dst (16-byte aligned) and stores its byte count in row_bytes[r].
+// Values: LoadValues, or ShareValues below (the row's shares computed from the secrets and the draws).  Crypt: EncPlain, or the
 // XSalsa20 keystream of the row's sealed box (EncXSalsa below), xor-ed into every unit on its way from the tile to global
 // memory.  The write cursor depends on the data (a step emits 8..81 units), so the keystream follows the cursor: a step whose
 // units reach past what the keystream tile holds stores the units it still covers, refills, and stores the rest.
-template <class Crypt>
-__device__ __forceinline__ void encode_row(const VarintRows& R, uint64_t r, uint8_t* __restrict__ dst, uint8_t* tile,
+template <class Values, class Crypt>
+__device__ __forceinline__ void encode_row(Values& vals, uint64_t len, uint64_t r, uint8_t* __restrict__ dst, uint8_t* tile,
                                            uint64_t* __restrict__ row_bytes, Crypt& crypt) {
     const int lane = threadIdx.x & 63;
-    const int64_t* __restrict__ src = R.values + r * R.row_stride;
     uint32_t* tile32 = reinterpret_cast<uint32_t*>(tile);
     uint4* tile128 = reinterpret_cast<uint4*>(tile);
-    const bool vec = (((uintptr_t)src) & 15u) == 0;
-    const uint64_t n_steps = (R.len + kEncVals - 1) / kEncVals;
-    const uint64_t len = R.len;
-    int64_t wx[kStreamDepth], wy[kStreamDepth];
-#pragma unroll
-    for (int d = 0; d < kStreamDepth; ++d) enc_load2(src, len, vec, (uint64_t)d * kEncVals + 2 * (uint64_t)lane, wx[d], wy[d]);
+    const uint64_t n_steps = (len + kEncVals - 1) / kEncVals;
     uint64_t cur = 0;                 // bytes of this row already in global memory (multiple of 16)
     uint32_t cb = 0;                  // carried bytes (< 16), held by lane 0 in `carry`
     uint4 carry = make_uint4(0, 0, 0, 0);
-    for (uint64_t j0 = 0; j0 < n_steps; j0 += kStreamDepth) {
+    for (uint64_t j0 = 0; j0 < n_steps; j0 += Values::kDepth) {
 #pragma unroll
-        for (int d = 0; d < kStreamDepth; ++d) {
+        for (int d = 0; d < Values::kDepth; ++d) {
             const uint64_t j = j0 + d;
             if (j >= n_steps) continue;
-            int64_t x = wx[d], y = wy[d];
-            asm volatile("" : "+v"(x), "+v"(y));
-            __builtin_amdgcn_sched_barrier(0);
-            enc_load2(src, len, vec, (j + kStreamDepth) * kEncVals + 2 * (uint64_t)lane, wx[d], wy[d]);
-            __builtin_amdgcn_sched_barrier(0);
+            int64_t x, y;
+            vals.get(d, j, x, y);
             const uint64_t i = j * kEncVals + 2 * (uint64_t)lane;
             const uint64_t zx = zigzag(x), zy = zigzag(y);
             const uint32_t lx = i < len ? varint_len(zx) : 0u, ly = i + 1 < len ? varint_len(zy) : 0u;
@@ -724,7 +743,9 @@ __global__ __launch_bounds__(kStreamWaves * 64) void varint_stream_encode_kernel
     const uint64_t r = (uint64_t)blockIdx.x * kStreamWaves + wave;
     if (r >= R.rows) return;
     EncPlain crypt;
-    encode_row(R, r, out + r * slot, tiles[wave], row_bytes, crypt);
+    LoadValues vals;
+    vals.open(R.values + r * R.row_stride, R.len);
+    encode_row(vals, R.len, r, out + r * slot, tiles[wave], row_bytes, crypt);
 }
 
 // ---- wire format -> clerk sums without the decoded tile ---------------------------------
@@ -1087,7 +1108,115 @@ __global__ __launch_bounds__(kStreamWaves * 64) void varint_seal_stream_kernel(V
     if (states[r].bad) { if ((threadIdx.x & 63) == 0) msg_bytes[r] = 0; return; }
     EncXSalsa crypt;
     crypt.open(states[r], kstream[wave]);
-    encode_row(R, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
+    LoadValues vals;
+    vals.open(R.values + r * R.row_stride, R.len);
+    encode_row(vals, R.len, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
+}
+
+// ---- secrets -> sealed clerking-job rows without the shares (participate.rs:75-101: share the secrets, seal every clerk's vector) ---
+// The seal kernel above with the row's shares COMPUTED instead of loaded.  Row r = c * participants + p is clerk c's vector of
+// participant p: one share per batch of k secrets.  The lane layout of the encode loop is the layout of the DPP-quad CSPRNG
+// (drbg_quad.hpp): lane l of step j holds batches 2 * pair and 2 * pair + 1 with pair = 64 j + l, a quad holds one group of 8
+// batches, so drbg_pair() gives the lane exactly the draws of its two batches.  All 64 lanes call it in every step - the lanes
+// past the row's end too (a quad must be whole); encode_row gives their values the length 0.
+//   additive      : clerk c < n - 1 gets draw c; the last clerk the secret minus all n - 1 draws (additive.rs:42-47)
+//   packed Shamir : clerk c < direct_rows gets draw c (systematic share map); every other clerk the dot product of its matrix row
+//                   with [k secrets ; t draws] - 128-bit sums folded every four terms, one REDC (as packed_gen_generic_kernel).
+//                   The row's address is wave-uniform: its coefficients arrive through scalar loads.
+// Every clerk wave derives the draws of its batches again: a participation costs up to n times the ChaCha blocks of
+// generate_batch_dev (clerks that receive a draw itself compute one draw per batch, not t).
+template <int ROUNDS>
+struct ShareValues {
+    static constexpr int kDepth = 1;          // nothing is prefetched: the step loop stays rolled
+    const ShareJob& J;
+    const int64_t* __restrict__ sp;          // the participant's secrets
+    const uint64_t* __restrict__ row;        // packed, dot-product clerk: k + t coefficients (Montgomery form); else nullptr
+    uint64_t stream;
+    uint32_t T, draw;                         // draws per batch; draw >= T: not a clerk that receives a draw itself
+    QuadCol qc;
+    __device__ __forceinline__ ShareValues(const ShareJob& J_, uint32_t c, uint64_t p) : J(J_) {
+        sp = J.secrets + p * J.secrets_stride;
+        stream = J.first_participant + p;
+        qc = quad_col(J.key);
+        T = J.additive ? J.n - 1 : J.t;
+        const uint32_t direct = J.additive ? J.n - 1 : J.direct_rows;
+        draw = c < direct ? c : T;
+        row = J.additive || c < direct ? nullptr : J.M + (uint64_t)(c - direct) * (J.k + J.t);
+    }
+    __device__ __forceinline__ void get(int, uint64_t j, int64_t& x, int64_t& y) {
+        const uint64_t pair = j * (kEncVals / 2) + (threadIdx.x & 63u);
+        const uint64_t b0 = 2 * pair;
+        const uint64_t m = J.mod.m, mu = J.mod.mu;
+        uint64_t r0, r1;
+        if (draw < T) {                                               // wave-uniform, as every branch and loop bound below
+            drbg_pair<ROUNDS>(J.key, qc, stream, pair, T, draw, J.mod, r0, r1);
+            x = (int64_t)r0; y = (int64_t)r1;
+            return;
+        }
+        if (J.additive) {
+            uint64_t s0 = b0 < J.len ? canon_i64(sp[b0], m, mu) : 0;
+            uint64_t s1 = b0 + 1 < J.len ? canon_i64(sp[b0 + 1], m, mu) : 0;
+            for (uint32_t i = 0; i < T; ++i) {
+                drbg_pair<ROUNDS>(J.key, qc, stream, pair, T, i, J.mod, r0, r1);
+                s0 = submod(s0, r0, m);
+                s1 = submod(s1, r1, m);
+            }
+            x = (int64_t)s0; y = (int64_t)s1;
+            return;
+        }
+        U128 a0{0, 0}, a1{0, 0};
+        uint32_t since = 0;
+        const uint64_t e0 = b0 * J.k, e1 = e0 + J.k;                  // the last batch is zero padded (batched.rs:37-43)
+        for (uint32_t i = 0; i < J.k; ++i) {
+            const uint64_t v0 = e0 + i < J.len ? canon_i64(sp[e0 + i], m, mu) : 0;
+            const uint64_t v1 = e1 + i < J.len ? canon_i64(sp[e1 + i], m, mu) : 0;
+            const uint64_t cf = row[i];
+            mac128(a0, cf, v0);
+            mac128(a1, cf, v1);
+            if (++since == 4) { mont_acc_condsub(a0, J.mont.p); mont_acc_condsub(a1, J.mont.p); since = 0; }
+        }
+        for (uint32_t i = 0; i < T; ++i) {
+            drbg_pair<ROUNDS>(J.key, qc, stream, pair, T, i, J.mod, r0, r1);
+            const uint64_t cf = row[J.k + i];
+            mac128(a0, cf, r0);
+            mac128(a1, cf, r1);
+            if (++since == 4) { mont_acc_condsub(a0, J.mont.p); mont_acc_condsub(a1, J.mont.p); since = 0; }
+        }
+        mont_acc_condsub(a0, J.mont.p);
+        mont_acc_condsub(a1, J.mont.p);
+        x = (int64_t)mont_redc(a0, J.mont.p, J.mont.pinv);
+        y = (int64_t)mont_redc(a1, J.mont.p, J.mont.pinv);
+    }
+};
+
+// One wave per row.  by_rows == 0: the kStreamWaves waves of a workgroup take kStreamWaves clerks of ONE participant (workgroup
+// p * ceil(n / kStreamWaves) + q holds clerks kStreamWaves q ..), so that participant's secrets come from HBM once per workgroup
+// and from the cache for its other waves.  by_rows != 0 (A/B only): consecutive rows, i.e. kStreamWaves participants of one
+// clerk, each wave fetching secrets of its own.
+template <int ROUNDS>
+__global__ __launch_bounds__(kStreamWaves * 64) void share_seal_stream_kernel(ShareJob J, uint32_t by_rows, uint8_t* __restrict__ boxes,
+                                                                              uint64_t slot, const SboxState* __restrict__ states,
+                                                                              uint64_t* __restrict__ msg_bytes) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kStreamWaves][kEncTile];
+    __shared__ uint32_t kstream[kStreamWaves][kKsTile];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint64_t c, p;
+    if (by_rows) {
+        const uint64_t r = (uint64_t)blockIdx.x * kStreamWaves + wave;
+        c = r / J.participants; p = r - c * J.participants;
+    } else {
+        const uint32_t groups = (J.n + kStreamWaves - 1) / kStreamWaves;
+        p = blockIdx.x / groups;
+        c = (uint64_t)(blockIdx.x - p * groups) * kStreamWaves + wave;
+    }
+    if (c >= J.n || p >= J.participants) return;
+    const uint64_t r = c * J.participants + p;
+    // a clerk key that gave the all-zero shared secret: that clerk's rows are refused (varint_seal_stream_kernel)
+    if (states[r].bad) { if ((threadIdx.x & 63) == 0) msg_bytes[r] = 0; return; }
+    EncXSalsa crypt;
+    crypt.open(states[r], kstream[wave]);
+    ShareValues<ROUNDS> vals(J, (uint32_t)c, p);
+    encode_row(vals, J.batches, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
@@ -1164,6 +1293,22 @@ hipError_t launch_varint_seal_stream(const VarintRows& R, uint8_t* d_boxes, size
     const uint64_t groups = vceil(R.rows, kStreamWaves);
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     varint_seal_stream_kernel<<<dim3((unsigned)groups), dim3(kStreamWaves * 64), 0, s>>>(R, d_boxes, slot_bytes, d_states, d_msg_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                    uint64_t* d_msg_bytes, hipStream_t s) {
+    if (J.participants == 0 || J.n == 0) return hipSuccess;
+    const bool by_rows = knob(KNOB_GENSEAL_BY_ROWS) != 0;
+    const uint64_t groups = by_rows ? vceil((uint64_t)J.n * J.participants, kStreamWaves) : vceil(J.n, kStreamWaves) * (uint64_t)J.participants;
+    if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)groups), block(kStreamWaves * 64);
+    switch (rounds) {
+        case 20: share_seal_stream_kernel<20><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        case 12: share_seal_stream_kernel<12><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        case 8: share_seal_stream_kernel<8><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

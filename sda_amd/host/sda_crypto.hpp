@@ -243,6 +243,44 @@ struct ShareEncryptor {
         return out;
     }
 };
+/// new_participation's sharing and encryption (participate.rs:75-101) for ONE participant through ONE call
+/// (sda_share_generator_generate_sealed_rows_dev): the secrets go in, clerk c's encryption comes out at index c, and no share is
+/// written to device memory on the way.  Device CSPRNG, canonical values, additive or packed Shamir with
+/// secret_count + privacy_threshold <= 32.  esk: null, or share_count * 32 injected ephemeral secrets (tests only).
+inline std::vector<Encryption> generate_sealed(ShareGenerator& gen, ShareCodec& codec, SealedBox& box,
+                                               const std::vector<EncryptionKey>& clerk_keys, const std::vector<Secret>& secrets,
+                                               const uint8_t* esk = nullptr) {
+    const size_t n = sda_share_generator_share_count(gen.h);
+    if (clerk_keys.size() != n) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "generate_sealed: one key per clerk");
+    std::vector<uint8_t> pks;
+    for (const auto& k : clerk_keys) {
+        if (k.size() != 32) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "generate_sealed: a clerk key is 32 bytes");
+        pks.insert(pks.end(), k.begin(), k.end());
+    }
+    const size_t B = sda_share_generator_batch_count(gen.h, secrets.size()), slot = sda_varint_slot_size(B) + SDA_SEALBYTES;
+    struct Dev {                                                    // freed on every way out
+        void* p = nullptr;
+        ~Dev() { if (p) sda_dev_free(p); }
+    } d_secrets, d_boxes, d_lens;
+    detail::check(sda_dev_malloc(&d_secrets.p, secrets.size() * sizeof(Secret) + 16));
+    detail::check(sda_dev_malloc(&d_boxes.p, n * slot));
+    detail::check(sda_dev_malloc(&d_lens.p, n * sizeof(uint64_t)));
+    if (!secrets.empty()) detail::check(sda_dev_upload(d_secrets.p, secrets.data(), secrets.size() * sizeof(Secret)));
+    detail::check(sda_share_generator_generate_sealed_rows_dev(gen.h, codec.h, box.h, pks.data(), esk, static_cast<const int64_t*>(d_secrets.p), 1,
+                                                               secrets.size(), secrets.size(), 0, static_cast<uint8_t*>(d_boxes.p), slot,
+                                                               static_cast<uint64_t*>(d_lens.p), nullptr));
+    detail::check(sda_dev_synchronize());
+    std::vector<uint64_t> lens(n);
+    detail::check(sda_dev_download(lens.data(), d_lens.p, n * sizeof(uint64_t)));
+    std::vector<Encryption> out;
+    for (size_t c = 0; c < n; ++c) {
+        if (lens[c] == 0) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "sealing refused: a clerk public key is a small-order point");
+        Encryption e(lens[c]);
+        detail::check(sda_dev_download(e.data(), static_cast<const uint8_t*>(d_boxes.p) + c * slot, lens[c]));
+        out.push_back(std::move(e));
+    }
+    return out;
+}
 struct ShareDecryptor {
     EncryptionKey pk; DecryptionKey sk; SealedBox box; ShareCodec codec;
     ShareDecryptor(EncryptionKey p, DecryptionKey s) : pk(std::move(p)), sk(std::move(s)) {}
