@@ -60,6 +60,11 @@ int  sda_debug_env_knobs_compiled_in(void);              /* 1 only in an SDA_AB_
  * _generate_combine_dev call on this thread, named as rocprofv3 prints them ("fused_packed_l31_kernel<3, 1, 20>";
  * two launches: "packed_gen_fft_kernel<...> + combine_update_walk_kernel (side stream)").  bench.py prints this as roofline.kernel. */
 const char* sda_debug_last_kernel(void);
+/* (Test library only.)  The kernel instance the last sda_secret_reconstructor_reconstruct_dev (or _reconstruct) call on this thread
+ * launched: "packed_reconstruct_n31_kernel<16, 4>" (NMAX, GROUP), "packed_reconstruct_vec_kernel<8>" (NMAX), or the any-shape kernel
+ * with its partition of a batch's k secrets, "packed_reconstruct_kernel groups=9 e_per_group=2".  It has a buffer of its own:
+ * sda_debug_last_kernel() is not changed by a reveal.  For tests/test_reveal_limits_gpu.py. */
+const char* sda_debug_last_reveal_kernel(void);
 /* The kernel-selection table without a device or a handle (sda_amd/csrc/path_select.hpp: the ONE place the decision is made):
  * `knobs` = comma-separated selection knob names from the list above (NULL or "" = defaults; the process-wide knob state is not
  * read; SDA_NO_LAZY and SDA_FFT_G, the per-handle knobs of the transform kernel's plan, are taken too, the latter with its value:

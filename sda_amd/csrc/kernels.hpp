@@ -59,6 +59,10 @@ struct N31Params {
 // The library reports what it ran (include/sda_hip_debug.h: sda_debug_last_kernel): every share-generation launcher names
 // the kernel instance it is about to launch, as rocprofv3 will print it (sda_capi.cpp keeps the last name per thread).
 void note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// The same for the one-shot reveal (sda_debug_last_reveal_kernel, test library only), in a buffer of its own: sda_debug_last_kernel
+// keeps reporting the last share-generation call whatever reveals follow it.  The grouped kernel is named with its partition:
+// "packed_reconstruct_kernel groups=9 e_per_group=2".
+void note_reveal_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
 // strides in elements
 struct GenLayout {

@@ -175,7 +175,15 @@ void sda::note_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* sda_debug_last_kernel(void) { return g_last_call_kernels; }
+static thread_local char g_last_reveal_kernel[96];     // the last one-shot reveal kernel instance launched on this thread
+void sda::note_reveal_kernel(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_reveal_kernel, sizeof g_last_reveal_kernel, fmt, ap);
+    va_end(ap);
+}
 #ifdef SDA_TEST_HOOKS
+extern "C" const char* sda_debug_last_reveal_kernel(void) { return g_last_reveal_kernel; }
 extern "C" int sda_debug_stream_create(void** stream) {
     if (!stream) return fail(SDA_ERR_INVALID_ARGUMENT, "stream is NULL");
     hipStream_t s = nullptr;

@@ -2317,6 +2317,7 @@ hipError_t launch_packed_reconstruct_n31(const int64_t* d_shares, size_t row_str
     } while (0)
     if (n_rows <= 4) RN(4); else if (n_rows <= 8) RN(8); else RN(16);
 #undef RN
+    note_reveal_kernel("packed_reconstruct_n31_kernel<%d, %d>", n_rows <= 4 ? 4 : n_rows <= 8 ? 8 : 16, g16 ? 16 : 4);
     return hipGetLastError();
 }
 
@@ -2336,6 +2337,7 @@ hipError_t launch_packed_reconstruct(const int64_t* d_shares, size_t row_stride,
             packed_reconstruct_vec_kernel<8><<<dim3((unsigned)vblocks), dim3(kThreads), lds, s>>>(d_shares, row_stride, n_rows, k, batches, dimension, mod, mont, d_Rmont, d_out);
         else
             packed_reconstruct_vec_kernel<16><<<dim3((unsigned)vblocks), dim3(kThreads), lds, s>>>(d_shares, row_stride, n_rows, k, batches, dimension, mod, mont, d_Rmont, d_out);
+        note_reveal_kernel("packed_reconstruct_vec_kernel<%d>", n_rows <= 4 ? 4 : n_rows <= 8 ? 8 : 16);
         return hipGetLastError();
     }
     const uint64_t blocks = ceil_div(batches, kThreads);
@@ -2347,6 +2349,7 @@ hipError_t launch_packed_reconstruct(const int64_t* d_shares, size_t row_stride,
     groups = ceil_div(k, e_per_group);
     packed_reconstruct_kernel<<<dim3((unsigned)blocks, (unsigned)groups), dim3(kThreads), 0, s>>>(d_shares, row_stride, n_rows, k, batches,
                                                                                                  dimension, mod, mont, d_Rmont, d_out, e_per_group);
+    note_reveal_kernel("packed_reconstruct_kernel groups=%u e_per_group=%u", (unsigned)groups, e_per_group);
     return hipGetLastError();
 }
 

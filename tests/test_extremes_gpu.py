@@ -7,14 +7,15 @@ each family admits: 2^62 - 57 for the wide families, 2^31 - 1 and the primes on 
 8355691 for the narrow limb GEMM.  Per case: injected generation against coracle.packed_generate; the device CSPRNG through
 generate_batch_dev in both share maps (odd row stride once per family) against coracle.packed_generate_csprng; for the families
 with a dual-role form two tiles through generate_combine_dev with every clerk row of the sums against coracle.combine; the round
-trip through reconstruct; and sda_debug_last_kernel() names the family that ran (every generation call; the reconstruct
-kernels record no name, see RECON below).  tests/test_extremes_reach.py checks on the CPU
+trip through reconstruct; and sda_debug_last_kernel() names the family that ran (every generation call; the reveal kernels have
+a name hook of their own, see RECON below).  tests/test_extremes_reach.py checks on the CPU
 that the crafted batches do reach the bounds; tests/test_path_select.py pins the selection at these primes."""
 import numpy as np
 import pytest
 
 import extremes as X
-from conftest import set_knob
+import reveal_limits
+from conftest import set_knob, use_test_hooks
 
 pytestmark = pytest.mark.gpu
 
@@ -137,18 +138,24 @@ def test_share_generation_at_the_limits(gpu, case):
 
 # (k, t, n, p, row stride kind): 3 / 7 / 15 rows take packed_reconstruct_vec_kernel<4 | 8 | 16> above 2^31 and the n31 reveal
 # below (4 terms per reduction at 2^31 - 1, 16 at 8355691); 33 rows or an odd row stride take the grouped kernel
-# (launch_packed_reconstruct's general form).  This routing follows from sda_secret_reconstructor_reconstruct_dev and is NOT
-# asserted: the reconstruct launches record no kernel name (sda_debug_last_kernel covers share generation only).
+# (launch_packed_reconstruct's general form).  The routing is asserted: sda_debug_last_reveal_kernel() (test library) against
+# reveal_limits.route().  Shares of p - 1 are the UNSIGNED worst case, that of the two 64-bit kernels, which sum canonical
+# products; the narrow kernel centres its values first and p - 1 centres to -1, so its sums stay 2^-28 below their bound here -
+# its worst case, rows sign-aligned with its constants, lives in tests/test_reveal_limits_gpu.py.
 RECON = [(k, t, n, p, odd) for p in (X.PMAX, X.P31MAX, X.NGEMM_PMAX)
          for k, t, n, odd in ((1, 2, 4, False), (3, 4, 8, False), (8, 7, 26, False), (20, 13, 50, False), (8, 7, 26, True))]
 
 
 @pytest.mark.parametrize("k,t,n,p,odd", RECON, ids=[f"k{c[0]}t{c[1]}n{c[2]}-p{c[3]}" + ("-odd" if c[4] else "") for c in RECON])
 def test_reconstruct_maximal_shares(gpu, k, t, n, p, odd):
-    """every share p - 1, mixed with 0 and 1: the reconstruct kernels' sums at their largest, against the oracle"""
+    """every share p - 1, mixed with 0 and 1, against the oracle: the sums of the two 64-bit reconstruct kernels at their largest
+    (canonical products).  NOT the narrow kernel's: it centres p - 1 to -1 (tests/test_reveal_limits_reach.py shows how far below
+    its bound that stays; tests/test_reveal_limits_gpu.py holds its sign-aligned worst case).  The kernel that ran is asserted."""
+    from sda_amd import capi
     from sda_amd import crypto
     from sda_amd.device import DeviceBuffer
     from oracle import coracle
+    use_test_hooks()                                      # the reveal's name hook exists in the test library only
     w2, w3 = X.omegas(p, k, t, n)
     B = 1500
     dim = B * k - (1 if k > 1 else 0)
@@ -165,6 +172,7 @@ def test_reconstruct_maximal_shares(gpu, k, t, n, p, odd):
     d_out = DeviceBuffer(dim + 1)
     rec = crypto.SecretReconstructor(crypto.PackedShamir(k, n, t, p, w2, w3), dim)
     assert rec.reconstruct_dev(idx, d_sh.ptr, B, stride, d_out.ptr, dim + 1) == dim
+    assert capi.load().sda_debug_last_reveal_kernel().decode() == reveal_limits.route(p, k, rows, d_sh.ptr % 16 == 0, d_out.ptr % 16 == 0, stride, B)[0]
     got = d_out.to_numpy()[:dim]
     want = coracle.packed_reconstruct(p, k, t, w2, w3, dim, idx, sh)
     assert np.array_equal(got, want)
