@@ -726,6 +726,30 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   other clerks' rows are intact.  Ephemeral secrets are uploaded, used and wiped as in seal_rows_dev.  Uses the
  *                   sealed-box handle's scratch: the one-stream-at-a-time rule holds.
  *
+ *   sda_share_combiner_finish_sealed_rows_dev : clerk.rs:84-100 in one call - the clerk's last step: the sums of a device job
+ *                   (sda_share_combiner_begin_dev(jobs, dimension) and its updates) are reduced, zig-zag varint encoded and sealed
+ *                   to the recipient's key pk.  Row j is job j's result at d_boxes + j * slot_bytes, d_row_bytes[j] = payload
+ *                   bytes + 48: the slotted layout sda_secret_reconstructor_update_sealed_rows_dev and open_rows_dev take.  Every
+ *                   box and length is byte for byte what sda_share_combiner_finish_dev followed by
+ *                   sda_sealedbox_seal_share_rows_dev (n_pks = 1, rows_per_key = rows = jobs, len = row_stride = dimension) write
+ *                   under the same ephemeral secrets (esk: NULL = OS entropy, else jobs * 32 bytes, TESTS ONLY).  A clerk has one
+ *                   result row per job, and the one-wave-per-row seal would put it on one wave: here every row is cut into blocks
+ *                   of 2048 values, one workgroup each.  After the setup pass a first kernel folds the 128-bit sums and counts
+ *                   each block's bytes, a scan places the blocks, and a second kernel folds the sums again, encodes the block
+ *                   and xors the XSalsa20 keystream of exactly its byte range into it while it is in LDS; the Poly1305 pass
+ *                   over the ciphertext stores the tags.  The canonical residues and their plaintext varints never reach HBM:
+ *                   there is no result buffer and no wire buffer, the only scratch is 12 bytes per block on the codec handle.
+ *                   Like finish_dev the call leaves the job's state valid - more updates and another finish may follow - and it
+ *                   joins the combiner's cross-stream ordering.  A recipient key of small order refuses every row exactly as
+ *                   seal_share_rows_dev does: d_row_bytes[j] = 0, the epk written, nothing past byte 32 of the slot touched.
+ *                   Nothing is written past byte d_row_bytes[j] of a live row's slot.  dimension == 0 gives `jobs` 48-byte boxes
+ *                   of the empty message.  SDA_ERR_INVALID_ARGUMENT before any launch for: a NULL handle or pointer, slot_bytes
+ *                   not a multiple of 16 or below sda_varint_slot_size(dimension) + 48, d_boxes not 16-byte aligned, the three
+ *                   handles not on one device.  SDA_ERR_STATE when the job was not begun with begin_dev;
+ *                   SDA_VALUES_RUST_SIGNED -> SDA_ERR_UNSUPPORTED, as the wire-fed updates (finish_dev + seal_share_rows_dev
+ *                   serve it).  Ephemeral secrets are uploaded, used and wiped as in seal_rows_dev.  Uses the sealed-box handle's
+ *                   scratch and the codec's: the one-stream-at-a-time rule holds for both.
+ *
  *   sda_mask_combiner_update_sealed_rows_dev : receive.rs:101-118 from the participants' sealed mask encryptions - an update
  *                   form of the mask combiner's device job (sda_mask_combiner_begin_dev above), rows laid out as for
  *                   open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does (d_ok[r] when d_ok is given;
@@ -789,6 +813,10 @@ int  sda_share_generator_generate_sealed_rows_dev(sda_share_generator_t* g, sda_
                                                   const int64_t* d_secrets, size_t participants, size_t len, size_t secrets_stride,
                                                   uint64_t first_participant, uint8_t* d_boxes, size_t slot_bytes,
                                                   uint64_t* d_row_bytes, void* stream);
+int  sda_share_combiner_finish_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                               const uint8_t pk[32] /* the recipient's key */,
+                                               const uint8_t* esk /* NULL = OS entropy; else jobs*32, tests only */,
+                                               uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, void* stream);
 int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
                                                const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,

@@ -203,6 +203,8 @@ SIGNATURES = {
     "sda_share_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
                                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                             C.c_void_p]),
+    "sda_share_combiner_finish_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                            C.c_void_p]),
     "sda_mask_combiner_begin_dev": (C.c_int, [_H, C.c_size_t, C.c_void_p]),
     "sda_mask_combiner_update_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]),
     "sda_mask_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

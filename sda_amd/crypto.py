@@ -320,25 +320,21 @@ class ShareCombiner(_Handle):
                                                                   d_row_bytes, rows, max_box_bytes, d_ok or None, d_status,
                                                                   stream or None))
 
-    def combine_sealed_job(self, blob, pk: bytes, sk: bytes, dimension: int) -> np.ndarray:
-        """clerk.rs:78-86 for an SDAJOBv1 blob of sealed boxes: open every encryption, decode it, sum the share vectors.
-        One bad box fails the job ("Sodium decryption failure"), so does a payload that does not hold `dimension` shares
-        ("Wrong dimension")."""
+    def _sum_sealed_job(self, what: str, blob, pk: bytes, sk: bytes, dimension: int, codec: "VarintCodec", box: "SealedBox") -> int:
+        """begin_dev(1, dimension) + update_sealed_rows_dev over an SDAJOBv1 blob of sealed boxes, its failures raised as the
+        reference's; returns the number of rows (0: nothing was begun)"""
         from .device import DeviceBuffer, DeviceBytes
         job = JobContainer.parse(bytes(blob))
         L = job.layout
         if L.payload_kind != capi.JOB_SEALED:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, "combine_sealed_job needs a job of sealed boxes (payload kind SEALED)")
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{what} needs a job of sealed boxes (payload kind SEALED)")
         if L.rows == 0:
-            return np.zeros(0, dtype=np.int64)                       # combiner.rs:17
+            return 0
         d_job = DeviceBytes.from_bytes(job.blob)
         d_status = DeviceBuffer(1).zero()
-        d_sums = DeviceBuffer(max(dimension, 1))
-        codec, box = VarintCodec(), SealedBox()
         self.begin_dev(1, dimension)
         self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes, d_job.ptr + L.lengths_offset,
                                     L.rows, L.slot_bytes, d_status.ptr)
-        self.finish_dev(d_sums.ptr)
         status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
         if status & 16:
             raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
@@ -346,7 +342,45 @@ class ShareCombiner(_Handle):
             raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")                    # combiner.rs:21
         if status:
             raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        return L.rows
+
+    def combine_sealed_job(self, blob, pk: bytes, sk: bytes, dimension: int) -> np.ndarray:
+        """clerk.rs:78-86 for an SDAJOBv1 blob of sealed boxes: open every encryption, decode it, sum the share vectors.
+        One bad box fails the job ("Sodium decryption failure"), so does a payload that does not hold `dimension` shares
+        ("Wrong dimension")."""
+        from .device import DeviceBuffer
+        if self._sum_sealed_job("combine_sealed_job", blob, pk, sk, dimension, VarintCodec(), SealedBox()) == 0:
+            return np.zeros(0, dtype=np.int64)                       # combiner.rs:17
+        d_sums = DeviceBuffer(max(dimension, 1))
+        self.finish_dev(d_sums.ptr)
         return d_sums.to_numpy()[:dimension].copy()
+
+    def finish_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", recipient_pk: bytes, d_boxes: int, slot_bytes: int,
+                               d_row_bytes: int, esk: Optional[bytes] = None, stream: int = 0) -> None:
+        """the clerk's last step (clerk.rs:84-100) on the device job: job j's sums reduced, varint encoded and sealed to the
+        recipient into d_boxes + j * slot_bytes, d_row_bytes[j] = payload + 48 (0: refused) - every row split over the whole
+        chip, no plaintext result and no wire buffer.  The job stays valid.  esk injects jobs*32 bytes (tests only)."""
+        assert len(recipient_pk) == 32
+        check(self._lib.sda_share_combiner_finish_sealed_rows_dev(self._h, codec._h, box._h, recipient_pk, esk, d_boxes, slot_bytes,
+                                                                  d_row_bytes, stream or None))
+
+    def clerk_sealed_job(self, blob, pk: bytes, sk: bytes, recipient_pk: bytes, dimension: int, esk: Optional[bytes] = None) -> bytes:
+        """process_clerking_job (clerk.rs:71-100) for an SDAJOBv1 blob of sealed boxes: combine_sealed_job, then the sums sealed
+        to the recipient - the clerking result's encryption.  Neither a share nor a sum is written to device memory in plain.
+        A job without rows gives the encryption of the empty vector (combiner.rs:17)."""
+        from .device import DeviceBuffer, DeviceBytes
+        assert esk is None or len(esk) == 32
+        codec, box = VarintCodec(), SealedBox()
+        if self._sum_sealed_job("clerk_sealed_job", blob, pk, sk, dimension, codec, box) == 0:
+            dimension = 0
+            self.begin_dev(1, 0)
+        slot = int(self._lib.sda_varint_slot_size(dimension)) + 48
+        d_box, d_len = DeviceBytes(slot), DeviceBuffer(1).zero()
+        self.finish_sealed_rows_dev(codec, box, recipient_pk, d_box.ptr, slot, d_len.ptr, esk)
+        n = int(d_len.to_numpy()[0])
+        if n == 0:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "sealing refused: the recipient public key is a small-order point")
+        return d_box.to_bytes()[:n]
 
     def set_residency(self, max_workgroups_per_cu: int) -> None:
         check(self._lib.sda_share_combiner_set_residency(self._h, max_workgroups_per_cu))

@@ -395,6 +395,20 @@ struct ShareJob {
 };
 hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
                                     uint64_t* d_msg_bytes, hipStream_t s);
+// clerk sums -> the ciphertext of the sealed clerking results, every row split over the chip (clerk.rs:84-100): job j's `len`
+// 128-bit sums are folded mod m, encoded and encrypted into d_boxes + j * slot_bytes + 48 under d_states[j], in blocks of 2048
+// values (sum_seal_blocks(len) per job, one workgroup each).  launch_sum_lengths writes the blocks' byte counts
+// (jobs * sum_seal_blocks(len) entries, job-major), launch_scan_u32 scans them, launch_sum_seal_wide takes the scan and writes the
+// bytes and d_msg_bytes[j]; a row whose state says `bad` is left alone (length 0).  Residues and plaintext bytes stay on the chip.
+struct SumRows {
+    const uint64_t* acc_lo;  const int64_t* acc_hi;   // [jobs][len]
+    size_t jobs, len;
+    uint64_t m, mu;
+};
+size_t sum_seal_blocks(size_t len);
+hipError_t launch_sum_lengths(const SumRows& S, uint32_t* d_block_bytes, hipStream_t s);
+hipError_t launch_sum_seal_wide(const SumRows& S, const uint64_t* d_block_off, uint8_t* d_boxes, size_t slot_bytes,
+                                const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t s);
 hipError_t launch_varint_rowcheck(const uint8_t* d_bytes, size_t n_bytes, const uint64_t* d_offsets, size_t rows,
                                   size_t len, const uint64_t* d_block_val_off, uint32_t* d_status, hipStream_t s);
 

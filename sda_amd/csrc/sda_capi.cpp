@@ -2886,6 +2886,39 @@ extern "C" int sda_share_generator_generate_sealed_rows_dev(sda_share_generator_
     return SDA_OK;
 }
 
+// the clerk's last step (clerk.rs:84-100): the sums reduced, encoded and sealed to the recipient, every row split over the chip -
+// setup, block lengths, scan, ONE pass that reduces, encodes and encrypts, tags.  No plaintext result, no wire buffer.
+extern "C" int sda_share_combiner_finish_sealed_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                         const uint8_t pk[32], const uint8_t* esk, uint8_t* d_boxes, size_t slot_bytes,
+                                                         uint64_t* d_row_bytes, void* stream) {
+    if (!c || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!pk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL recipient key");
+    if (!d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    if (capi_sealedbox_device(b) != codec->ctx.device || c->ctx.device != codec->ctx.device)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the combiner lives on device %d, the sealed-box handle on device %d, the codec on device %d",
+                    c->ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    if (!c->begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the sealed finish folds 128-bit sums: SDA_VALUES_RUST_SIGNED takes finish_dev + seal_share_rows_dev");
+    const size_t L = c->dimension;
+    if (L > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(L) + SDA_SEALBYTES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(dimension) + 48");
+    if (c->jobs == 0) return SDA_OK;
+    SDA_TRY(c->ctx.use());
+    hipStream_t s = c->ctx.pick(stream);
+    const size_t nb = c->jobs * sum_seal_blocks(L);               // the only scratch of the call: 12 bytes per 2048 values
+    SDA_TRY(codec->d_blocks.reserve(nb * 4));
+    SDA_TRY(codec->d_offs.reserve(nb * 8));
+    SDA_TRY(codec->d_aux.reserve(scan_aux_entries(nb) * 8));
+    SDA_TRY(c->join_pending(s));
+    const SumRows S{c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), c->jobs, L, c->mod.m, c->mod.mu};
+    SDA_TRY(capi_sealedbox_seal_summed_rows(b, pk, esk, S, codec->d_blocks.as<uint32_t>(), codec->d_offs.as<uint64_t>(),
+                                            codec->d_total.as<uint64_t>(), codec->d_aux.as<uint64_t>(), d_boxes, slot_bytes, d_row_bytes, s));
+    note_kernel("sum_len_kernel + sum_seal_wide_kernel + sbox_poly_kernel");         // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return c->mark_pending(s);
+}
+
 extern "C" int sda_share_combiner_update_varint(sda_share_combiner_t* c, sda_varint_codec_t* codec, const uint8_t* bytes,
                                                 size_t n_bytes) {
     if (!c || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");

@@ -195,6 +195,30 @@ int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, con
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing generated share rows: launch failed: %s", hipGetErrorString(e));
 }
 
+// for sda_share_combiner_finish_sealed_rows_dev (sda_capi.cpp), which has checked the arguments and reserved the scan scratch
+// (d_block_bytes / d_block_off: jobs * sum_seal_blocks(len) entries; d_scan_aux: scan_aux_entries of that; d_scan_total: 8 bytes):
+// as above with the rows computed from the clerk sums and every row split over the chip - lengths, scan, encode + encrypt
+int capi_sealedbox_seal_summed_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const SumRows& S, uint32_t* d_block_bytes,
+                                    uint64_t* d_block_off, uint64_t* d_scan_total, uint64_t* d_scan_aux, uint8_t* d_boxes,
+                                    size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
+    const size_t rows = S.jobs, max_msg = S.len * 10;
+    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
+    if (int st = scratch(b, rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
+    uint8_t *d_esk = nullptr, *d_pks = nullptr;
+    if (int st = stage_keys(b, pk, 1, esk, rows, s, &d_esk, &d_pks)) return st;
+    SboxState* d_states = static_cast<SboxState*>(b->d_states);
+    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
+    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, 1, rows, d_boxes, slot_bytes, rows, d_states, s);
+    if (e == hipSuccess) e = launch_sum_lengths(S, d_block_bytes, s);
+    if (e == hipSuccess && S.len) e = launch_scan_u32(d_block_bytes, d_block_off, rows * sum_seal_blocks(S.len), d_scan_total, d_scan_aux, s);
+    if (e == hipSuccess) e = launch_sum_seal_wide(S, d_block_off, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    if (e == hipSuccess)
+        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing summed rows: launch failed: %s", hipGetErrorString(e));
+}
+
 int capi_sealedbox_device(const sda_sealedbox* b) { return b->device; }
 
 // ---- host forms: one payload, staged through the device (what ShareEncryptor::encrypt / ShareDecryptor::decrypt call) ----

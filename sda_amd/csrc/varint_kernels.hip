@@ -1219,6 +1219,118 @@ __global__ __launch_bounds__(kStreamWaves * 64) void share_seal_stream_kernel(Sh
     encode_row(vals, J.batches, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
 }
 
+// ---- clerk sums -> the sealed clerking result, every row split over the chip (clerk.rs:84-100: reduce, encode_var, seal) ---------
+// A clerk has ONE result row per job, so the one-wave-per-row seal above would put a whole job on one wave.  Here a row is cut
+// into blocks of kSumVals values, one workgroup each, in the three passes of the scan-form encoder - lengths, scan, write - with
+// the residues computed from the 128-bit accumulators in the first and the third pass (mod_i128, the fold of
+// combine_finish_kernel) and the XSalsa20 keystream xor-ed into the block's bytes while they sit in LDS.  Neither the residues nor
+// the plaintext varint bytes reach memory; the accumulators are read twice (32 B per value).
+//
+// Geometry: a block whose bytes start at message byte `off` covers stream bytes [32 + off, 32 + off + total) (stream bytes
+// 0..31 are the Poly1305 key), i.e. the Salsa20 blocks from (32 + off) >> 6 on.  The stage is laid on that block grid - its byte
+// 0 is the first byte of Salsa20 block (32 + off) >> 6, the block's own bytes start at pad = (32 + off) & 63 - so keystream
+// word x of the workgroup belongs to stage word x.  The keystream tile is [block][17 words]: lane i stores its block with a stride
+// of 17 words (no bank shared inside a wave), the xor pass reads it with consecutive lanes on consecutive words.
+static constexpr int kSumVals = kVT * kVals;                  // values per workgroup
+static constexpr int kSumStage = 64 + kSumVals * 10;          // pad (< 64) + at most 10 bytes per value
+static constexpr int kSumKsBlocks = kSumStage / 64;           // Salsa20 blocks that can overlap the stage: 321, one or two per lane
+static constexpr int kSumKsStride = 17;
+
+size_t sum_seal_blocks(size_t len) { return (size_t)((len + kSumVals - 1) / kSumVals); }
+
+// Only the block total matters: value i of the block goes to lane i % 256 (coalesced 8-byte loads).
+__global__ __launch_bounds__(kVT) void sum_len_kernel(SumRows S, uint32_t* __restrict__ block_bytes) {
+    __shared__ uint32_t waves[kVT / 64];
+    const uint64_t job = blockIdx.y;
+    const uint64_t* lo = S.acc_lo + job * S.len;
+    const int64_t* hi = S.acc_hi + job * S.len;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kSumVals + threadIdx.x;
+    uint32_t sum = 0;
+    for (int u = 0; u < kVals; ++u) {
+        const uint64_t i = i0 + (uint64_t)u * kVT;
+        if (i < S.len) sum += varint_len(zigzag((int64_t)mod_i128(lo[i], hi[i], S.m, S.mu)));
+    }
+    uint32_t total;
+    (void)block_exscan(sum, waves, &total);
+    if (threadIdx.x == 0) block_bytes[job * gridDim.x + blockIdx.x] = total;
+}
+
+// Workgroup (blk, job): the block's residues again, their varint bytes into the stage (8 consecutive values per lane, as
+// varint_write_kernel), the keystream of exactly the Salsa20 blocks the stage overlaps, the xor, and the copy into the box with
+// varint_write_kernel's rule (bytes up to the destination's first dword boundary, dwords, tail bytes: two workgroups never store
+// to the same dword).  block_off: the exclusive scan of sum_len_kernel's totals over all jobs; a block's offset inside its row is
+// its entry minus that of its job's first block.  The job's last block stores the row's message length for the Poly1305 pass.
+// A row whose state says `bad` (all-zero shared secret) is not encoded: length 0, nothing written.
+__global__ __launch_bounds__(kVT) void sum_seal_wide_kernel(SumRows S, const uint64_t* __restrict__ block_off, uint8_t* __restrict__ boxes,
+                                                            uint64_t slot, const SboxState* __restrict__ states,
+                                                            uint64_t* __restrict__ msg_bytes) {
+    __shared__ uint32_t waves[kVT / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kSumStage + 16];
+    __shared__ uint32_t ks[kSumKsBlocks * kSumKsStride];
+    const uint64_t job = blockIdx.y, blk = blockIdx.x, n_blk = gridDim.x;
+    const bool last = blk + 1 == n_blk;
+    const SboxState& st = states[job];
+    if (st.bad) { if (last && threadIdx.x == 0) msg_bytes[job] = 0; return; }       // workgroup-uniform
+    const uint64_t off = block_off[job * n_blk + blk] - block_off[job * n_blk];
+    const uint32_t pad = (uint32_t)((off + 32) & 63u);
+    const uint64_t ks0 = (off + 32) >> 6;                     // the Salsa20 block under stage byte 0
+    const uint64_t* lo = S.acc_lo + job * S.len;
+    const int64_t* hi = S.acc_hi + job * S.len;
+    const uint64_t i0 = blk * kSumVals + (uint64_t)threadIdx.x * kVals;
+    uint64_t zz[kVals];
+    uint32_t ln[kVals];
+    uint32_t sum = 0;
+    for (int k = 0; k < kVals; ++k) {
+        zz[k] = 0; ln[k] = 0;
+        if (i0 + k < S.len) {
+            zz[k] = zigzag((int64_t)mod_i128(lo[i0 + k], hi[i0 + k], S.m, S.mu));
+            ln[k] = varint_len(zz[k]);
+            sum += ln[k];
+        }
+    }
+    uint32_t total;
+    uint32_t pos = pad + block_exscan(sum, waves, &total);
+#pragma unroll
+    for (int k = 0; k < kVals; ++k) {
+        if (ln[k]) {
+            uint64_t n = zz[k];
+            for (uint32_t b = 0; b + 1 < ln[k]; ++b) { stage[pos++] = (uint8_t)(0x80u | (n & 0x7Fu)); n >>= 7; }
+            stage[pos++] = (uint8_t)n;
+        }
+    }
+    if (total) {
+        uint32_t key[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) key[i] = st.subkey[i];
+        const uint32_t n_ks = (pad + total + 63u) >> 6;       // <= kSumKsBlocks
+        for (uint32_t i = threadIdx.x; i < n_ks; i += kVT) {
+            uint32_t b[16];
+            sbx::salsa20_block(b, key, st.n0, st.n1, ks0 + i);
+#pragma unroll
+            for (int w = 0; w < 16; ++w) ks[i * kSumKsStride + w] = b[w];
+        }
+    }
+    __syncthreads();
+    uint32_t* stage32 = reinterpret_cast<uint32_t*>(stage);
+    const uint32_t n_words = total ? (pad + total + 3u) >> 2 : 0u;                   // whole words: the bytes around the block's never leave
+    for (uint32_t x = threadIdx.x; x < n_words; x += kVT) stage32[x] ^= ks[(x >> 4) * kSumKsStride + (x & 15u)];
+    __syncthreads();
+    uint8_t* dst = boxes + job * slot + 48 + off;
+    const uint32_t head = (uint32_t)((4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u);
+    const uint32_t h = head < total ? head : total;
+    if (threadIdx.x < h) dst[threadIdx.x] = stage[pad + threadIdx.x];
+    const uint32_t n_dw = (total - h) >> 2;
+    uint32_t* dst32 = reinterpret_cast<uint32_t*>(dst + h);
+    for (uint32_t d = threadIdx.x; d < n_dw; d += kVT) {
+        const uint32_t byte = pad + h + 4u * d;                // source byte offset in stage
+        const uint32_t w0 = stage32[byte >> 2], w1 = stage32[(byte >> 2) + 1];
+        dst32[d] = __builtin_amdgcn_alignbyte(w1, w0, byte & 3u);
+    }
+    const uint32_t done = h + 4u * n_dw;
+    if (threadIdx.x < total - done) dst[done + threadIdx.x] = stage[pad + done + threadIdx.x];
+    if (last && threadIdx.x == 0) msg_bytes[job] = off + total;
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 static inline uint64_t vceil(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
@@ -1293,6 +1405,31 @@ hipError_t launch_varint_seal_stream(const VarintRows& R, uint8_t* d_boxes, size
     const uint64_t groups = vceil(R.rows, kStreamWaves);
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     varint_seal_stream_kernel<<<dim3((unsigned)groups), dim3(kStreamWaves * 64), 0, s>>>(R, d_boxes, slot_bytes, d_states, d_msg_bytes);
+    return hipGetLastError();
+}
+
+static bool sum_grid(const SumRows& S, dim3* grid) {
+    const uint64_t nb = sum_seal_blocks(S.len);
+    if (S.jobs > 65535 || nb * S.jobs > 0xFFFFFFFFull / kVT) return false;          // grid.y; < 2^32 work-items per launch
+    *grid = dim3((unsigned)nb, (unsigned)S.jobs);
+    return true;
+}
+
+hipError_t launch_sum_lengths(const SumRows& S, uint32_t* d_block_bytes, hipStream_t s) {
+    if (S.jobs == 0 || S.len == 0) return hipSuccess;
+    dim3 grid;
+    if (!sum_grid(S, &grid)) return hipErrorInvalidConfiguration;
+    sum_len_kernel<<<grid, dim3(kVT), 0, s>>>(S, d_block_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_seal_wide(const SumRows& S, const uint64_t* d_block_off, uint8_t* d_boxes, size_t slot_bytes,
+                                const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t s) {
+    if (S.jobs == 0) return hipSuccess;
+    if (S.len == 0) return hipMemsetAsync(d_msg_bytes, 0, S.jobs * sizeof(uint64_t), s);   // no block: every row is the empty message
+    dim3 grid;
+    if (!sum_grid(S, &grid)) return hipErrorInvalidConfiguration;
+    sum_seal_wide_kernel<<<grid, dim3(kVT), 0, s>>>(S, d_block_off, d_boxes, slot_bytes, d_states, d_msg_bytes);
     return hipGetLastError();
 }
 

@@ -205,6 +205,30 @@ struct SealedBox {
         return out;
     }
 };
+/// The clerk's last step (clerk.rs:84-100) for a StreamingShareCombiner's job through ONE call
+/// (sda_share_combiner_finish_sealed_rows_dev): the sums are reduced, encoded and sealed to the recipient, the row split over the
+/// whole chip; neither the result nor its wire bytes are written to device memory in plain.  The job stays valid.  esk: null, or
+/// 32 injected bytes of ephemeral secret (tests only).
+inline Encryption finish_sealed(StreamingShareCombiner& comb, ShareCodec& codec, SealedBox& box, const EncryptionKey& recipient_pk,
+                                const uint8_t* esk = nullptr) {
+    if (recipient_pk.size() != 32) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "finish_sealed: the recipient key is 32 bytes");
+    const size_t slot = sda_varint_slot_size(comb.dimension) + SDA_SEALBYTES;
+    struct Dev {                                                    // freed on every way out
+        void* p = nullptr;
+        ~Dev() { if (p) sda_dev_free(p); }
+    } d_box, d_len;
+    detail::check(sda_dev_malloc(&d_box.p, slot));
+    detail::check(sda_dev_malloc(&d_len.p, sizeof(uint64_t)));
+    detail::check(sda_share_combiner_finish_sealed_rows_dev(comb.h, codec.h, box.h, recipient_pk.data(), esk, static_cast<uint8_t*>(d_box.p), slot,
+                                                            static_cast<uint64_t*>(d_len.p), nullptr));
+    detail::check(sda_dev_synchronize());
+    uint64_t len = 0;
+    detail::check(sda_dev_download(&len, d_len.p, sizeof len));
+    if (len == 0) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "sealing refused: the recipient public key is a small-order point");
+    Encryption e(len);
+    detail::check(sda_dev_download(e.data(), d_box.p, len));
+    return e;
+}
 struct ShareEncryptor {
     EncryptionKey pk; SealedBox box; ShareCodec codec;
     explicit ShareEncryptor(EncryptionKey k) : pk(std::move(k)) {}
