@@ -245,72 +245,58 @@ hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride
                                  int64_t* d_mask, size_t mask_stride, int64_t* d_masked, size_t masked_stride, hipStream_t s);
 
 // ---- rand-0.3 ChaChaRng mask expansion (chacha.rs:36-39, :60-73) ----------------------------------
-// Adds the `dimension` masks of each of the n_seeds seeds into the 128-bit accumulators.
-// d_seeds: n_seeds x 8 u32 key words (seed words beyond the given ones are 0).
-// Fast path: candidate i of every seed is added at position i (correct unless the seed's stream
-// contains a rejected candidate).  d_rejects[s] (zeroed by the caller) counts the rejected candidates of
-// seed s among its first `dimension` and keeps the index of up to three of them; such seeds must then be
-// corrected by launch_chacha_mask_shift (count <= 3) or launch_chacha_mask_slow(subtract_naive = true).
-struct RejectRecord {
+// The i-th mask of a seed is its i-th ACCEPTED candidate.  One sequence serves every caller, and no launch in it waits for a
+// result: fast pass (candidate i taken for mask i, rejections recorded per seed), launch_chacha_mask_plan (the records -> two
+// lists and their lengths, on the device), launch_chacha_mask_shift_listed (1..3 rejections) and launch_chacha_mask_slow_listed
+// (more) - or the exact-order launcher alone, over every key, where rejections are the rule.
+// d_seeds: 8 u32 key words per seed (seed words beyond the given ones are 0).
+// A count (of keys, of list entries) is `d_n, max`: the device word *d_n <= max, or max itself when d_n == nullptr.
+struct RejectRecord {     // of seed s, zeroed by the caller: the rejected among its first `dimension` candidates, and where up to three are
     uint32_t count;
     uint32_t pos[3];
 };
-hipError_t launch_chacha_mask_accumulate(const uint32_t* d_seeds, size_t n_seeds, size_t dimension,
-                                         const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo,
-                                         int64_t* d_acc_hi, RejectRecord* d_rejects, hipStream_t s);
-// Parallel correction of the seeds in d_list whose rejected candidates are all recorded (count 1..3): removing
-// candidate x shifts every later mask by one, so position i >= x takes candidate i + (rejections so far) instead of
-// candidate i - each lane recomputes two ChaCha blocks and adds the difference.  The last few positions reach
-// past candidate `dimension`, which the fast kernel never tested: those lanes walk on until they have their mask.
-hipError_t launch_chacha_mask_shift(const uint32_t* d_seeds, const uint32_t* d_list, size_t n_list,
-                                    const RejectRecord* d_rejects, size_t dimension, const ModParams& mod,
-                                    uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi, hipStream_t s);
-// exact sequential-order expansion (handles rejections) of the seeds named by d_list (n_list indices
-// into d_seeds; d_list == nullptr -> seeds 0..n_list-1), added into the accumulators.  With
-// subtract_naive the fast kernel's contribution for those seeds is taken back first.
-hipError_t launch_chacha_mask_slow(const uint32_t* d_seeds, const uint32_t* d_list, size_t n_list,
-                                   size_t dimension, const ModParams& mod, uint64_t zone,
-                                   uint64_t* d_acc_lo, int64_t* d_acc_hi, bool subtract_naive,
-                                   hipStream_t s);
-
-// ---- the same sums with every decision on the device (sda_mask_combiner_*_dev: no launch below waits for a result) ----
-// seed rows ([rows][row_len] int64, stride row_stride; words `as u32`, the first 8 count) -> 8 key words per row
-hipError_t launch_mask_rows_to_keys(const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride, uint32_t* d_keys,
-                                    hipStream_t s);
-// launch_chacha_mask_accumulate over the first *d_n_seeds (<= max_seeds, which sizes the grid) keys
-hipError_t launch_chacha_mask_accumulate_counted(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
-                                                 const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
-                                                 RejectRecord* d_rejects, hipStream_t s);
+// where the masks go: into the 128-bit column accumulators d_acc_lo / d_acc_hi (mask combine, chacha.rs:56-77; `apply` null), or
+// onto each participant's own secrets, out[s][i] = (secrets[s][i] + mask_i(seed s)) mod m (mask, chacha.rs:36-47)
+struct MaskApply {
+    const int64_t* secrets; size_t secrets_stride;
+    int64_t* out; size_t out_stride;
+    ModParams mod;
+};
+// fast pass into the accumulators: the candidates themselves are added (the sums are only read modulo m)
+hipError_t launch_chacha_mask_accumulate(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
+                                         uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi, RejectRecord* d_rejects,
+                                         hipStream_t s);
+// fast pass of the apply sink, one participant per seed
+hipError_t launch_chacha_apply_fast(const uint32_t* d_seeds, size_t participants, size_t dimension, uint64_t zone,
+                                    const MaskApply& apply, RejectRecord* d_rejects, hipStream_t s);
 // the repair plan from the fast pass's records: d_plan[0] seeds with 1..3 rejections into d_shift_list, d_plan[1] with more into
 // d_exact_list (both counters zeroed by the caller, both lists hold up to n entries, in no particular order)
 hipError_t launch_chacha_mask_plan(const RejectRecord* d_rejects, size_t n, uint32_t* d_plan, uint32_t* d_shift_list,
                                    uint32_t* d_exact_list, hipStream_t s);
-// launch_chacha_mask_shift / _slow over a list of *d_n_list (<= max_list) entries: a fixed, bounded grid whose workgroups stride
-// over the entries.  d_list == nullptr (exact order only): keys 0 .. *d_n_list - 1
+// Parallel correction of the seeds in d_list whose rejected candidates are all recorded (count 1..3): removing
+// candidate x shifts every later mask by one, so position i >= x takes candidate i + (rejections so far) instead of
+// candidate i - each lane recomputes two ChaCha blocks and adds the difference (apply: writes the mask's row anew).  The last
+// few positions reach past candidate `dimension`, which the fast pass never tested: those lanes walk on until they have their mask.
 hipError_t launch_chacha_mask_shift_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
                                            const RejectRecord* d_rejects, size_t dimension, uint64_t zone, uint64_t* d_acc_lo,
-                                           int64_t* d_acc_hi, hipStream_t s);
+                                           int64_t* d_acc_hi, const MaskApply* apply, hipStream_t s);
+// exact sequential-order expansion (handles rejections) of the seeds named by d_list (indices into d_seeds; d_list == nullptr:
+// seeds 0, 1, ...).  With subtract_naive the fast pass's contribution to the accumulators is taken back first (apply: no need,
+// the row is overwritten).
 hipError_t launch_chacha_mask_slow_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
                                           size_t dimension, const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo,
-                                          int64_t* d_acc_hi, bool subtract_naive, hipStream_t s);
+                                          int64_t* d_acc_hi, bool subtract_naive, const MaskApply* apply, hipStream_t s);
+
+// ---- where the mask combiner's device form gets its keys ----
+// seed rows ([rows][row_len] int64, stride row_stride; words `as u32`, the first 8 count) -> 8 key words per row
+hipError_t launch_mask_rows_to_keys(const int64_t* d_rows, size_t rows, size_t row_len, size_t row_stride, uint32_t* d_keys,
+                                    hipStream_t s);
 // sealed seed rows (box r at d_boxes + r * slot, tags checked by launch_sealedbox_verify: rows marked bad in d_states are skipped)
 // -> the keys of the rows that decrypt to a well-formed varint seed, packed from d_keys[0], their number added to *d_n_keys;
 // *d_status |= 1 (a value of more than 10 bytes) / 4 (ends inside a value) for a row that does not
 struct SboxState;
 hipError_t launch_sealed_seed_keys(const uint8_t* d_boxes, size_t slot, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
                                    const SboxState* d_states, uint32_t* d_keys, uint32_t* d_n_keys, uint32_t* d_status, hipStream_t s);
-
-// the same expansion applied to each participant's own vector: out[p][i] = (secrets[p][i] + mask_i(seed p)) mod m
-// (chacha.rs:36-47 for a device-resident tile).  Fast pass for every participant (rejections recorded in d_rejects,
-// zeroed by the caller), then the repair pass for the listed ones: shift list (1..3 rejections), exact-order list
-// (more; d_exact_list == nullptr walks participants 0..n_exact-1 in stream order and needs no fast pass).
-hipError_t launch_chacha_apply_fast(const uint32_t* d_seeds, size_t participants, size_t dimension, const ModParams& mod,
-                                    uint64_t zone, const int64_t* d_secrets, size_t secrets_stride, int64_t* d_out,
-                                    size_t out_stride, RejectRecord* d_rejects, hipStream_t s);
-hipError_t launch_chacha_apply_repair(const uint32_t* d_seeds, const uint32_t* d_shift_list, size_t n_shift,
-                                      const uint32_t* d_exact_list, size_t n_exact, const RejectRecord* d_rejects,
-                                      size_t dimension, const ModParams& mod, uint64_t zone, const int64_t* d_secrets,
-                                      size_t secrets_stride, int64_t* d_out, size_t out_stride, hipStream_t s);
 
 // ---- zig-zag LEB128 codec of share vectors (sodium.rs:36-41, :83-89) - varint_kernels.hip -------------
 struct VarintRows {

@@ -493,55 +493,6 @@ int column_sum_host(const Ctx& ctx, AccState& acc, DevBuf& tile, DevBuf& d_out, 
 // rand 0.3 Range<i64>: zone = u64::MAX - u64::MAX % range  
 uint64_t rand03_zone(uint64_t range) { return UINT64_MAX - (UINT64_MAX % range); }
 
-// Adds the masks of `n_seeds` ChaCha seeds (8 key words each, host) into acc.
-int chacha_accumulate(const Ctx& ctx, const std::vector<uint32_t>& seeds8, size_t n_seeds, size_t dimension,
-                      const ModParams& mod, AccState& acc, DevBuf& d_seeds, DevBuf& d_flags, DevBuf& d_list) {
-    if (n_seeds == 0 || dimension == 0) return SDA_OK;
-    const uint64_t zone = rand03_zone(mod.m);
-    // expected rejected candidates per seed: up to about one, nearly every seed is either clean or repaired by the
-    // parallel shift pass (<= 3 rejections); beyond that the exact-order kernel does everything
-    const double p_rej = (double)(UINT64_MAX - zone + 1) / 18446744073709551616.0;
-    const bool all_slow = p_rej * (double)dimension > 1.0 || dimension >= 0xFFFFFFF0ull;
-    const size_t chunk = (size_t)1 << 20;                  // seeds per launch
-    for (size_t s0 = 0; s0 < n_seeds; s0 += chunk) {
-        const size_t ns = std::min(chunk, n_seeds - s0);
-        SDA_TRY(d_seeds.reserve(ns * 32));
-        HIP_TRY(hipMemcpyAsync(d_seeds.p, seeds8.data() + s0 * 8, ns * 32, hipMemcpyHostToDevice, ctx.stream));
-        if (all_slow) {
-            HIP_TRY(launch_chacha_mask_slow(d_seeds.as<uint32_t>(), nullptr, ns, dimension, mod, zone, acc.lo.as<uint64_t>(),
-                                            acc.hi.as<int64_t>(), false, ctx.stream));
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-            continue;
-        }
-        SDA_TRY(d_flags.reserve(ns * sizeof(RejectRecord)));
-        HIP_TRY(hipMemsetAsync(d_flags.p, 0, ns * sizeof(RejectRecord), ctx.stream));
-        HIP_TRY(launch_chacha_mask_accumulate(d_seeds.as<uint32_t>(), ns, dimension, mod, zone, acc.lo.as<uint64_t>(),
-                                              acc.hi.as<int64_t>(), d_flags.as<RejectRecord>(), ctx.stream));
-        std::vector<RejectRecord> rec(ns);
-        HIP_TRY(hipMemcpyAsync(rec.data(), d_flags.p, ns * sizeof(RejectRecord), hipMemcpyDeviceToHost, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        std::vector<uint32_t> shift, exact;                 // seeds repaired in parallel / walked in stream order
-        for (size_t i = 0; i < ns; ++i)
-            if (rec[i].count) (rec[i].count <= 3 ? shift : exact).push_back((uint32_t)i);
-        if (!shift.empty() || !exact.empty()) {
-            SDA_TRY(d_list.reserve((shift.size() + exact.size()) * 4));
-            uint32_t* dl = d_list.as<uint32_t>();
-            if (!shift.empty()) {
-                HIP_TRY(hipMemcpyAsync(dl, shift.data(), shift.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-                HIP_TRY(launch_chacha_mask_shift(d_seeds.as<uint32_t>(), dl, shift.size(), d_flags.as<RejectRecord>(), dimension, mod,
-                                                 zone, acc.lo.as<uint64_t>(), acc.hi.as<int64_t>(), ctx.stream));
-            }
-            if (!exact.empty()) {
-                HIP_TRY(hipMemcpyAsync(dl + shift.size(), exact.data(), exact.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-                HIP_TRY(launch_chacha_mask_slow(d_seeds.as<uint32_t>(), dl + shift.size(), exact.size(), dimension, mod, zone,
-                                                acc.lo.as<uint64_t>(), acc.hi.as<int64_t>(), true, ctx.stream));
-            }
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-        }
-    }
-    return SDA_OK;
-}
-
 // host vectors that hold key or seed material: zeroed before the memory is released, on every exit path
 template <typename T>
 struct WipedVec : std::vector<T> {
@@ -2058,6 +2009,81 @@ struct MaskCore {
     }
     size_t seed_words() const { return (size_t)((scheme.seed_bitsize + 31) / 32); }   // chacha.rs:31
 };
+
+// ---- the rand-0.3 ChaCha mask expansion (chacha.rs:36-39, :60-73): one driver for every entry point ----
+// head of the plan scratch (MaskCore::d_list): three counters the kernels keep, then the two lists of a chunk
+enum { PLAN_SHIFT = 0, PLAN_EXACT = 1, PLAN_KEYS = 2, PLAN_HEAD = 4 };
+constexpr size_t kMaskChunk = (size_t)1 << 20;             // keys per run of the driver when the caller can split them
+
+// room for ns keys in c.d_seeds and for their repair plan, the plan's counters zeroed
+int mask_chunk_scratch(MaskCore& c, size_t ns, hipStream_t s) {
+    SDA_TRY(c.d_seeds.reserve_wiped(ns * 32));
+    SDA_TRY(c.d_flags.reserve(ns * sizeof(RejectRecord)));
+    SDA_TRY(c.d_list.reserve((PLAN_HEAD + 2 * ns) * 4));
+    HIP_TRY(hipMemsetAsync(c.d_list.p, 0, PLAN_HEAD * 4, s));
+    return SDA_OK;
+}
+
+// Rejections are the rule: the exact-order walk does everything.  With up to about one expected rejected candidate per seed
+// nearly every seed is clean or repaired by the parallel shift (<= 3 rejections) and the fast pass pays off; beyond that it
+// would be redone for most seeds.  A RejectRecord holds positions in 32 bits, so a dimension near 2^32 walks as well.
+// (modulus, dimension) alone decide: the host never needs a count from the device
+bool chacha_exact_order_for_all(uint64_t zone, size_t dimension) {
+    const double p_rej = (double)(UINT64_MAX - zone + 1) / 18446744073709551616.0;
+    return p_rej * (double)dimension > 1.0 || dimension >= 0xFFFFFFF0ull;
+}
+
+// The `dimension` masks of each of the ns keys in c.d_seeds (mask_chunk_scratch(c, ns) has been called; counted: of the first
+// plan[PLAN_KEYS] <= ns of them, a number only the device knows), added into c.acc or - apply, never counted - put onto every
+// key's own row.  Fast pass, the repair plan made and read on the device, list-driven shift and exact-order launches: nothing here
+// waits for the device or copies from it
+int chacha_expand(MaskCore& c, size_t ns, bool counted, size_t dimension, const MaskApply* apply, hipStream_t s) {
+    if (ns == 0 || dimension == 0) return SDA_OK;
+    const uint64_t zone = rand03_zone(c.mod.m);
+    const uint32_t* keys = c.d_seeds.as<uint32_t>();
+    uint32_t* plan = c.d_list.as<uint32_t>();
+    const uint32_t* n_keys = counted ? plan + PLAN_KEYS : nullptr;
+    uint64_t* lo = c.acc.lo.as<uint64_t>();
+    int64_t* hi = c.acc.hi.as<int64_t>();
+    if (chacha_exact_order_for_all(zone, dimension)) {
+        HIP_TRY(launch_chacha_mask_slow_listed(keys, nullptr, n_keys, ns, dimension, c.mod, zone, lo, hi, false, apply, s));
+        return SDA_OK;
+    }
+    RejectRecord* rej = c.d_flags.as<RejectRecord>();
+    HIP_TRY(hipMemsetAsync(rej, 0, ns * sizeof(RejectRecord), s));
+    if (apply) HIP_TRY(launch_chacha_apply_fast(keys, ns, dimension, zone, *apply, rej, s));
+    else HIP_TRY(launch_chacha_mask_accumulate(keys, n_keys, ns, dimension, zone, lo, hi, rej, s));
+    uint32_t* shift = plan + PLAN_HEAD;
+    uint32_t* exact = shift + ns;
+    HIP_TRY(launch_chacha_mask_plan(rej, ns, plan, shift, exact, s));
+    HIP_TRY(launch_chacha_mask_shift_listed(keys, shift, plan + PLAN_SHIFT, ns, rej, dimension, zone, lo, hi, apply, s));
+    HIP_TRY(launch_chacha_mask_slow_listed(keys, exact, plan + PLAN_EXACT, ns, dimension, c.mod, zone, lo, hi, true, apply, s));
+    return SDA_OK;
+}
+const char* const kMaskRepairKernels = "chacha_mask_plan_kernel + chacha_mask_shift_listed_kernel + chacha_mask_slow_listed_kernel";
+
+// the masks of n host keys summed into c.acc, a chunk at a time through c.d_seeds.  Only enqueues: `key8` is in flight until the
+// caller has synchronised s, which it does on every path (end_synchronised)
+int chacha_sum_host_keys(MaskCore& c, const uint32_t* key8, size_t n, size_t dimension, hipStream_t s) {
+    for (size_t k0 = 0; k0 < n; k0 += kMaskChunk) {
+        const size_t ns = std::min(kMaskChunk, n - k0);
+        SDA_TRY(mask_chunk_scratch(c, ns, s));
+        HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8 + k0 * 8, ns * 32, hipMemcpyHostToDevice, s));
+        SDA_TRY(chacha_expand(c, ns, false, dimension, nullptr, s));
+    }
+    return SDA_OK;
+}
+
+// a call that copies out of host vectors of its own: `enqueue` does every asynchronous step, and whatever became of it (its status
+// and message are kept) the stream is synchronised before those vectors die
+template <typename Enqueue>
+int end_synchronised(hipStream_t s, Enqueue&& enqueue) {
+    const int st = enqueue();
+    const hipError_t se = hipStreamSynchronize(s);
+    if (st != SDA_OK) return st;
+    HIP_TRY(se);
+    return SDA_OK;
+}
 }  // namespace
 
 struct sda_secret_masker { MaskCore core; };
@@ -2181,15 +2207,17 @@ extern "C" int sda_secret_masker_mask(sda_secret_masker_t* m, const int64_t* sec
     seed_to_key(seed.data(), nw, key8.data());
     if (len) {
         SDA_TRY(c.acc.reset(len, s));
-        SDA_TRY(chacha_accumulate(c.ctx, key8, 1, len, c.mod, c.acc, c.d_seeds, c.d_flags, c.d_list));
         SDA_TRY(c.d_a.reserve(len * 8));
         SDA_TRY(c.d_b.reserve(len * 8));
         SDA_TRY(c.d_out.reserve(len * 8));
-        HIP_TRY(launch_combine_finish(c.acc.lo.as<uint64_t>(), c.acc.hi.as<int64_t>(), len, c.mod, c.d_b.as<int64_t>(), s));
-        HIP_TRY(hipMemcpyAsync(c.d_a.p, secrets, len * 8, hipMemcpyHostToDevice, s));
-        SDA_TRY(c.addsub(c.d_a.as<int64_t>(), c.d_b.as<int64_t>(), len, false, c.d_out.as<int64_t>(), s));    // chacha.rs:41-44
-        HIP_TRY(hipMemcpyAsync(masked_out, c.d_out.p, len * 8, hipMemcpyDeviceToHost, s));
-        SDA_TRY(c.ctx.sync());
+        SDA_TRY(end_synchronised(s, [&]() -> int {
+            SDA_TRY(chacha_sum_host_keys(c, key8.data(), 1, len, s));
+            HIP_TRY(launch_combine_finish(c.acc.lo.as<uint64_t>(), c.acc.hi.as<int64_t>(), len, c.mod, c.d_b.as<int64_t>(), s));
+            HIP_TRY(hipMemcpyAsync(c.d_a.p, secrets, len * 8, hipMemcpyHostToDevice, s));
+            SDA_TRY(c.addsub(c.d_a.as<int64_t>(), c.d_b.as<int64_t>(), len, false, c.d_out.as<int64_t>(), s));    // chacha.rs:41-44
+            HIP_TRY(hipMemcpyAsync(masked_out, c.d_out.p, len * 8, hipMemcpyDeviceToHost, s));
+            return SDA_OK;
+        }));
     }
     for (size_t i = 0; i < nw; ++i) mask_out[i] = seed[i];                    // chacha.rs:48-50
     *mask_len = nw;
@@ -2225,38 +2253,13 @@ extern "C" int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const in
                 words[p * nw + i] = (int64_t)raw[p * nw + i];
                 if (i < 8) key8[p * 8 + i] = raw[p * nw + i];
             }
-        HIP_TRY(hipMemcpy2DAsync(d_masks, mask_stride * 8, words.data(), nw * 8, nw * 8, participants, hipMemcpyHostToDevice, s));
-        SDA_TRY(c.d_seeds.reserve(participants * 32));
-        HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8.data(), participants * 32, hipMemcpyHostToDevice, s));
-        const uint64_t zone = rand03_zone(c.mod.m);
-        const double p_rej = (double)(UINT64_MAX - zone + 1) / 18446744073709551616.0;
-        const uint32_t* seeds = c.d_seeds.as<uint32_t>();
-        if (p_rej * (double)len > 1.0 || len >= 0xFFFFFFF0ull) {               // rejections are the rule: exact order for all
-            HIP_TRY(launch_chacha_apply_repair(seeds, nullptr, 0, nullptr, participants, nullptr, len, c.mod, zone, d_secrets,
-                                               secrets_stride, d_masked, masked_stride, s));
-            HIP_TRY(hipStreamSynchronize(s));                                  // the host vectors above are in flight until here
-            return SDA_OK;
-        }
-        SDA_TRY(c.d_flags.reserve(participants * sizeof(RejectRecord)));
-        HIP_TRY(hipMemsetAsync(c.d_flags.p, 0, participants * sizeof(RejectRecord), s));
-        HIP_TRY(launch_chacha_apply_fast(seeds, participants, len, c.mod, zone, d_secrets, secrets_stride, d_masked, masked_stride,
-                                         c.d_flags.as<RejectRecord>(), s));
-        std::vector<RejectRecord> rec(participants);
-        HIP_TRY(hipMemcpyAsync(rec.data(), c.d_flags.p, participants * sizeof(RejectRecord), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        std::vector<uint32_t> shift, exact;
-        for (size_t p = 0; p < participants; ++p)
-            if (rec[p].count) (rec[p].count <= 3 ? shift : exact).push_back((uint32_t)p);
-        if (!shift.empty() || !exact.empty()) {
-            SDA_TRY(c.d_list.reserve((shift.size() + exact.size()) * 4));
-            uint32_t* dl = c.d_list.as<uint32_t>();
-            if (!shift.empty()) HIP_TRY(hipMemcpyAsync(dl, shift.data(), shift.size() * 4, hipMemcpyHostToDevice, s));
-            if (!exact.empty()) HIP_TRY(hipMemcpyAsync(dl + shift.size(), exact.data(), exact.size() * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(launch_chacha_apply_repair(seeds, dl, shift.size(), dl + shift.size(), exact.size(), c.d_flags.as<RejectRecord>(),
-                                               len, c.mod, zone, d_secrets, secrets_stride, d_masked, masked_stride, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        return SDA_OK;
+        SDA_TRY(mask_chunk_scratch(c, participants, s));
+        const MaskApply apply{d_secrets, secrets_stride, d_masked, masked_stride, c.mod};
+        return end_synchronised(s, [&]() -> int {                             // the host vectors above are in flight until it returns
+            HIP_TRY(hipMemcpy2DAsync(d_masks, mask_stride * 8, words.data(), nw * 8, nw * 8, participants, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8.data(), participants * 32, hipMemcpyHostToDevice, s));
+            return chacha_expand(c, participants, false, len, &apply, s);
+        });
     }
     if (c.scheme.kind == SDA_MASKING_NONE) {                                  // none.rs:13-19: identity, no mask
         HIP_TRY(hipMemcpy2DAsync(d_masked, masked_stride * 8, d_secrets, secrets_stride * 8, len * 8, participants,
@@ -2313,12 +2316,15 @@ extern "C" int sda_mask_combiner_combine(sda_mask_combiner_t* mc, const int64_t*
         seed_to_key(rows[r], row_lens[r], key8.data() + r * 8);
     }
     SDA_TRY(c.ctx.use());
-    SDA_TRY(c.acc.reset(dimension, c.ctx.stream));
-    SDA_TRY(chacha_accumulate(c.ctx, key8, n_rows, dimension, c.mod, c.acc, c.d_seeds, c.d_flags, c.d_list));
+    hipStream_t s = c.ctx.stream;
+    SDA_TRY(c.acc.reset(dimension, s));
     SDA_TRY(c.d_out.reserve(dimension * 8));
-    HIP_TRY(launch_combine_finish(c.acc.lo.as<uint64_t>(), c.acc.hi.as<int64_t>(), dimension, c.mod, c.d_out.as<int64_t>(), c.ctx.stream));
-    HIP_TRY(hipMemcpyAsync(out, c.d_out.p, dimension * 8, hipMemcpyDeviceToHost, c.ctx.stream));
-    SDA_TRY(c.ctx.sync());
+    SDA_TRY(end_synchronised(s, [&]() -> int {
+        SDA_TRY(chacha_sum_host_keys(c, key8.data(), n_rows, dimension, s));
+        SDA_TRY(acc_finish(c.acc, dimension, c.mod, c.d_out.as<int64_t>(), s));
+        HIP_TRY(hipMemcpyAsync(out, c.d_out.p, dimension * 8, hipMemcpyDeviceToHost, s));
+        return SDA_OK;
+    }));
     *out_len = dimension;
     return SDA_OK;
 }
@@ -2326,51 +2332,6 @@ extern "C" int sda_mask_combiner_combine(sda_mask_combiner_t* mc, const int64_t*
 // -------------------------------------------------------------------------------------------------
 // MaskCombiner, device form (receive.rs:101-118 with the masks in HBM): begin / update / finish, every update stream-ordered
 // -------------------------------------------------------------------------------------------------
-namespace {
-// head of the plan scratch (MaskCore::d_list): three counters the kernels keep, then the two lists of a chunk
-enum { PLAN_SHIFT = 0, PLAN_EXACT = 1, PLAN_KEYS = 2, PLAN_HEAD = 4 };
-constexpr size_t kMaskChunk = (size_t)1 << 20;             // seeds per launch, as chacha_accumulate
-
-int mask_chunk_scratch(MaskCore& c, size_t ns, hipStream_t s) {
-    SDA_TRY(c.d_seeds.reserve_wiped(ns * 32));
-    SDA_TRY(c.d_flags.reserve(ns * sizeof(RejectRecord)));
-    SDA_TRY(c.d_list.reserve((PLAN_HEAD + 2 * ns) * 4));
-    HIP_TRY(hipMemsetAsync(c.d_list.p, 0, PLAN_HEAD * 4, s));
-    return SDA_OK;
-}
-
-// chacha_accumulate for the ns (counted: at most ns, PLAN_KEYS of them) keys in c.d_seeds, with the repair plan made and read on
-// the device: fast pass, plan, list-driven shift and exact-order launches - or exact order for all when rejections are the rule,
-// which (modulus, dimension) alone decide
-int chacha_accumulate_dev(MaskCore& c, size_t ns, bool counted, hipStream_t s) {
-    const size_t dimension = c.job_dimension;
-    if (ns == 0 || dimension == 0) return SDA_OK;
-    const uint64_t zone = rand03_zone(c.mod.m);
-    const double p_rej = (double)(UINT64_MAX - zone + 1) / 18446744073709551616.0;
-    const bool all_slow = p_rej * (double)dimension > 1.0 || dimension >= 0xFFFFFFF0ull;
-    const uint32_t* keys = c.d_seeds.as<uint32_t>();
-    uint32_t* plan = c.d_list.as<uint32_t>();
-    uint64_t* lo = c.acc.lo.as<uint64_t>();
-    int64_t* hi = c.acc.hi.as<int64_t>();
-    if (all_slow) {
-        if (counted) HIP_TRY(launch_chacha_mask_slow_listed(keys, nullptr, plan + PLAN_KEYS, ns, dimension, c.mod, zone, lo, hi, false, s));
-        else HIP_TRY(launch_chacha_mask_slow(keys, nullptr, ns, dimension, c.mod, zone, lo, hi, false, s));
-        return SDA_OK;
-    }
-    RejectRecord* rej = c.d_flags.as<RejectRecord>();
-    HIP_TRY(hipMemsetAsync(rej, 0, ns * sizeof(RejectRecord), s));
-    if (counted) HIP_TRY(launch_chacha_mask_accumulate_counted(keys, plan + PLAN_KEYS, ns, dimension, c.mod, zone, lo, hi, rej, s));
-    else HIP_TRY(launch_chacha_mask_accumulate(keys, ns, dimension, c.mod, zone, lo, hi, rej, s));
-    uint32_t* shift = plan + PLAN_HEAD;
-    uint32_t* exact = shift + ns;
-    HIP_TRY(launch_chacha_mask_plan(rej, ns, plan, shift, exact, s));
-    HIP_TRY(launch_chacha_mask_shift_listed(keys, shift, plan + PLAN_SHIFT, ns, rej, dimension, zone, lo, hi, s));
-    HIP_TRY(launch_chacha_mask_slow_listed(keys, exact, plan + PLAN_EXACT, ns, dimension, c.mod, zone, lo, hi, true, s));
-    return SDA_OK;
-}
-const char* const kMaskRepairKernels = "chacha_mask_plan_kernel + chacha_mask_shift_listed_kernel + chacha_mask_slow_listed_kernel";
-}  // namespace
-
 extern "C" int sda_mask_combiner_begin_dev(sda_mask_combiner_t* mc, size_t dimension, void* stream) {
     if (!mc) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL");
     MaskCore& c = mc->core;
@@ -2415,7 +2376,7 @@ extern "C" int sda_mask_combiner_update_dev(sda_mask_combiner_t* mc, const int64
         const size_t ns = std::min(kMaskChunk, rows - r0);
         SDA_TRY(mask_chunk_scratch(c, ns, s));
         HIP_TRY(launch_mask_rows_to_keys(d_rows + r0 * row_stride, ns, row_len, row_stride, c.d_seeds.as<uint32_t>(), s));
-        SDA_TRY(chacha_accumulate_dev(c, ns, false, s));
+        SDA_TRY(chacha_expand(c, ns, false, c.job_dimension, nullptr, s));
     }
     note_kernel("mask_rows_to_keys_kernel + chacha_mask_fast_kernel + %s", kMaskRepairKernels);          // the whole call, not only its last launch
     snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
@@ -2458,7 +2419,7 @@ extern "C" int sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* mc,
         uint32_t* plan = c.d_list.as<uint32_t>();
         HIP_TRY(launch_sealed_seed_keys(d_boxes + r0 * slot_bytes, slot_bytes, d_row_bytes + r0, ns, max_box_bytes, d_states + r0,
                                         c.d_seeds.as<uint32_t>(), plan + PLAN_KEYS, d_status, s));
-        SDA_TRY(chacha_accumulate_dev(c, ns, true, s));
+        SDA_TRY(chacha_expand(c, ns, true, c.job_dimension, nullptr, s));
     }
     note_kernel("sbox_poly_kernel + sealed_seed_keys_kernel + chacha_mask_fast_counted_kernel + %s", kMaskRepairKernels);
     snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);

@@ -1341,12 +1341,11 @@ __device__ __forceinline__ void chacha_fast_body(const uint32_t* __restrict__ se
 }
 
 __global__ __launch_bounds__(kThreads) void chacha_mask_fast_kernel(const uint32_t* __restrict__ seeds,
-                                                                    size_t n_seeds, size_t dimension, ModParams mod,
+                                                                    size_t n_seeds, size_t dimension,
                                                                     uint64_t zone, uint64_t* __restrict__ acc_lo,
                                                                     int64_t* __restrict__ acc_hi,
                                                                     RejectRecord* __restrict__ rejects,
                                                                     size_t seeds_per_split) {
-    (void)mod;
     chacha_fast_body(seeds, n_seeds, dimension, zone, acc_lo, acc_hi, rejects, seeds_per_split);
 }
 
@@ -1370,20 +1369,14 @@ __device__ __forceinline__ uint64_t block_candidate(const uint32_t (&o)[16], uin
     return ((uint64_t)hi << 32) | lo;
 }
 
+// the APPLY sink (MaskApply, kernels.hpp): out[s][i] = (secrets[s][i] + candidate mod m) mod m
+__device__ __forceinline__ void mask_apply_put(const MaskApply& ap, uint32_t s, uint64_t i, uint64_t candidate) {
+    const uint64_t x = canon_i64(ap.secrets[(size_t)s * ap.secrets_stride + i], ap.mod.m, ap.mod.mu);
+    ap.out[(size_t)s * ap.out_stride + i] = (int64_t)addmod(x, barrett_mod64(candidate, ap.mod.m, ap.mod.mu), ap.mod.m);
+}
+
 // Shift correction for seeds whose <= 3 rejected candidates (all below `dimension`) are recorded: the mask of
 // position i is candidate f(i) = i + #{rejected <= f(i)} instead of candidate i.
-// where the masks go: into the 128-bit column accumulators (mask combine, chacha.rs:56-77), or - APPLY - onto a
-// participant's own secrets, out[s][i] = (secrets[s][i] + mask_i(seed s)) mod m (mask, chacha.rs:36-47)
-struct MaskApply {
-    const int64_t* secrets; size_t secrets_stride;
-    int64_t* out; size_t out_stride;
-    ModParams mod;
-    __device__ __forceinline__ void put(uint32_t s, uint64_t i, uint64_t candidate) const {
-        const uint64_t x = canon_i64(secrets[(size_t)s * secrets_stride + i], mod.m, mod.mu);
-        out[(size_t)s * out_stride + i] = (int64_t)addmod(x, barrett_mod64(candidate, mod.m, mod.mu), mod.m);
-    }
-};
-
 template <bool APPLY>
 __device__ __forceinline__ void chacha_shift_body(const uint32_t* __restrict__ seeds, const uint32_t s,
                                                   const RejectRecord* __restrict__ rejects, size_t dimension, uint64_t zone,
@@ -1433,7 +1426,7 @@ __device__ __forceinline__ void chacha_shift_body(const uint32_t* __restrict__ s
                 ++idx;
             }
         }
-        if (APPLY) ap.put(s, i, nv);                                      // overwrite what the fast pass wrote here
+        if (APPLY) mask_apply_put(ap, s, i, nv);                                     // overwrite what the fast pass wrote here
         else {
             const uint64_t ov = block_candidate(o0, m);                   // what the fast kernel added here
             acc_atomic_add(acc_lo + i, acc_hi + i, nv - ov, nv < ov ? -1 : 0);
@@ -1441,28 +1434,20 @@ __device__ __forceinline__ void chacha_shift_body(const uint32_t* __restrict__ s
     }
 }
 
+// ... for the entries of a list: workgroup row y takes entries y, y + gridDim.y, ... below the list's length, which is the
+// device word *n_list (the host never learns how many seeds need the repair; none for an empty list) or, with n_list == nullptr,
+// max_list
 template <bool APPLY>
-__global__ __launch_bounds__(kThreads) void chacha_mask_shift_kernel(const uint32_t* __restrict__ seeds,
-                                                                     const uint32_t* __restrict__ list,
-                                                                     const RejectRecord* __restrict__ rejects,
-                                                                     size_t dimension, uint64_t zone,
-                                                                     uint64_t* __restrict__ acc_lo,
-                                                                     int64_t* __restrict__ acc_hi, MaskApply ap) {
-    chacha_shift_body<APPLY>(seeds, list[blockIdx.y], rejects, dimension, zone, acc_lo, acc_hi, ap);
-}
-
-// ... driven by a list whose LENGTH lives on the device (mask combiner's device form: the host never learns how many seeds
-// need the repair): a fixed grid, workgroup row y takes entries y, y + gridDim.y, ... below *n_list - none for an empty list
 __global__ __launch_bounds__(kThreads) void chacha_mask_shift_listed_kernel(const uint32_t* __restrict__ seeds,
                                                                             const uint32_t* __restrict__ list,
-                                                                            const uint32_t* __restrict__ n_list,
+                                                                            const uint32_t* __restrict__ n_list, uint32_t max_list,
                                                                             const RejectRecord* __restrict__ rejects,
                                                                             size_t dimension, uint64_t zone,
                                                                             uint64_t* __restrict__ acc_lo,
-                                                                            int64_t* __restrict__ acc_hi) {
-    const uint32_t n = *n_list;
+                                                                            int64_t* __restrict__ acc_hi, MaskApply ap) {
+    const uint32_t n = n_list ? *n_list : max_list;
     for (uint32_t e = blockIdx.y; e < n; e += gridDim.y)
-        chacha_shift_body<false>(seeds, list[e], rejects, dimension, zone, acc_lo, acc_hi, MaskApply{});
+        chacha_shift_body<APPLY>(seeds, list[e], rejects, dimension, zone, acc_lo, acc_hi, ap);
 }
 
 // APPLY fast pass: participant s = blockIdx.y of the slice, one lane = one ChaCha block = 8 positions
@@ -1486,7 +1471,7 @@ __global__ __launch_bounds__(kThreads) void chacha_mask_apply_kernel(const uint3
             const uint32_t k = atomicAdd(&rejects[s].count, 1u);
             if (k < 3) rejects[s].pos[k] = (uint32_t)(pos0 + m);
         }
-        ap.put(s, pos0 + m, v);
+        mask_apply_put(ap, s, pos0 + m, v);
     }
 }
 
@@ -1539,7 +1524,7 @@ __device__ __forceinline__ void chacha_slow_body(const uint32_t* __restrict__ se
             }
             if (okmask & (1u << m)) {
                 if (pos < dimension) {
-                    if (APPLY) ap.put(s, pos, r[m]);
+                    if (APPLY) mask_apply_put(ap, s, pos, r[m]);
                     else acc_atomic_add(acc_lo + pos, acc_hi + pos, r[m], 0);
                 }
                 ++pos;
@@ -1552,33 +1537,22 @@ __device__ __forceinline__ void chacha_slow_body(const uint32_t* __restrict__ se
     }
 }
 
-template <bool APPLY>
-__global__ __launch_bounds__(kThreads) void chacha_mask_slow_kernel(const uint32_t* __restrict__ seeds,
-                                                                    const uint32_t* __restrict__ list, size_t dimension,
-                                                                    ModParams mod, uint64_t zone,
-                                                                    uint64_t* __restrict__ acc_lo,
-                                                                    int64_t* __restrict__ acc_hi, bool subtract_naive,
-                                                                    MaskApply ap) {
-    __shared__ uint32_t wave_tot[kThreads / 64];
-    __shared__ uint32_t chunk_total;
-    chacha_slow_body<APPLY>(seeds, list ? list[blockIdx.x] : blockIdx.x, dimension, mod, zone, acc_lo, acc_hi, subtract_naive, ap,
-                            wave_tot, chunk_total);
-}
-
-// ... over a list (nullptr: keys 0 .. *n_list - 1) whose length lives on the device: a fixed grid, workgroup x walks entries
+// ... over a list (nullptr: keys 0, 1, ...) whose length is *n_list or, with n_list == nullptr, max_list: workgroup x walks entries
 // x, x + gridDim.x, ... one after the other (every walk ends on a barrier, so the shared scan words are free again)
+template <bool APPLY>
 __global__ __launch_bounds__(kThreads) void chacha_mask_slow_listed_kernel(const uint32_t* __restrict__ seeds,
                                                                            const uint32_t* __restrict__ list,
-                                                                           const uint32_t* __restrict__ n_list, size_t dimension,
-                                                                           ModParams mod, uint64_t zone,
+                                                                           const uint32_t* __restrict__ n_list, uint32_t max_list,
+                                                                           size_t dimension, ModParams mod, uint64_t zone,
                                                                            uint64_t* __restrict__ acc_lo,
-                                                                           int64_t* __restrict__ acc_hi, bool subtract_naive) {
+                                                                           int64_t* __restrict__ acc_hi, bool subtract_naive,
+                                                                           MaskApply ap) {
     __shared__ uint32_t wave_tot[kThreads / 64];
     __shared__ uint32_t chunk_total;
-    const uint32_t n = *n_list;
+    const uint32_t n = n_list ? *n_list : max_list;
     for (uint32_t e = blockIdx.x; e < n; e += gridDim.x)
-        chacha_slow_body<false>(seeds, list ? list[e] : e, dimension, mod, zone, acc_lo, acc_hi, subtract_naive, MaskApply{},
-                                wave_tot, chunk_total);
+        chacha_slow_body<APPLY>(seeds, list ? list[e] : e, dimension, mod, zone, acc_lo, acc_hi, subtract_naive, ap, wave_tot,
+                                chunk_total);
 }
 
 // ---- the mask combiner's device form (chacha.rs:56-77 with nothing on the host) ----------------------------------------
@@ -2390,46 +2364,25 @@ hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride
     return hipGetLastError();
 }
 
-hipError_t launch_chacha_mask_accumulate(const uint32_t* d_seeds, size_t n_seeds, size_t dimension,
-                                         const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
-                                         RejectRecord* d_rejects, hipStream_t s) {
-    if (n_seeds == 0 || dimension == 0) return hipSuccess;
+hipError_t launch_chacha_mask_accumulate(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
+                                         uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi, RejectRecord* d_rejects,
+                                         hipStream_t s) {
+    if (max_seeds == 0 || dimension == 0) return hipSuccess;
     const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
     if (hipError_t e = grid_check(pos_blocks)) return e;
     const uint64_t want_blocks = 256 * 8;
     uint64_t split = 1;
     if (pos_blocks < want_blocks) split = ceil_div(want_blocks, pos_blocks);
-    if (split > n_seeds) split = n_seeds;
+    if (split > max_seeds) split = max_seeds;
     if (split > 65535) split = 65535;
-    const size_t per = ceil_div(n_seeds, split);
-    split = ceil_div(n_seeds, per);
-    chacha_mask_fast_kernel<<<dim3((unsigned)pos_blocks, (unsigned)split), dim3(kThreads), 0, s>>>(
-        d_seeds, n_seeds, dimension, mod, zone, d_acc_lo, d_acc_hi, d_rejects, per);
-    return hipGetLastError();
-}
-
-hipError_t launch_chacha_mask_shift(const uint32_t* d_seeds, const uint32_t* d_list, size_t n_list,
-                                    const RejectRecord* d_rejects, size_t dimension, const ModParams& mod, uint64_t zone,
-                                    uint64_t* d_acc_lo, int64_t* d_acc_hi, hipStream_t s) {
-    (void)mod;
-    if (n_list == 0 || dimension == 0) return hipSuccess;
-    const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
-    if (hipError_t e = grid_check(pos_blocks)) return e;
-    for (size_t l0 = 0; l0 < n_list; l0 += 65535) {
-        const unsigned nl = (unsigned)(n_list - l0 < 65535 ? n_list - l0 : 65535);
-        chacha_mask_shift_kernel<false><<<dim3((unsigned)pos_blocks, nl), dim3(kThreads), 0, s>>>(
-            d_seeds, d_list + l0, d_rejects, dimension, zone, d_acc_lo, d_acc_hi, MaskApply{});
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_chacha_mask_slow(const uint32_t* d_seeds, const uint32_t* d_list, size_t n_list, size_t dimension,
-                                   const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
-                                   bool subtract_naive, hipStream_t s) {
-    if (n_list == 0 || dimension == 0) return hipSuccess;
-    if (hipError_t e = grid_check(n_list)) return e;
-    chacha_mask_slow_kernel<false><<<dim3((unsigned)n_list), dim3(kThreads), 0, s>>>(d_seeds, d_list, dimension, mod, zone,
-                                                                                     d_acc_lo, d_acc_hi, subtract_naive, MaskApply{});
+    const size_t per = ceil_div(max_seeds, split);
+    split = ceil_div(max_seeds, per);
+    const dim3 grid((unsigned)pos_blocks, (unsigned)split);
+    if (d_n_seeds)      // the grid is sized for the upper bound: a split past *d_n_seeds has an empty seed loop
+        chacha_mask_fast_counted_kernel<<<grid, dim3(kThreads), 0, s>>>(d_seeds, d_n_seeds, dimension, zone, d_acc_lo, d_acc_hi,
+                                                                        d_rejects, per);
+    else
+        chacha_mask_fast_kernel<<<grid, dim3(kThreads), 0, s>>>(d_seeds, max_seeds, dimension, zone, d_acc_lo, d_acc_hi, d_rejects, per);
     return hipGetLastError();
 }
 
@@ -2453,25 +2406,6 @@ hipError_t launch_sealed_seed_keys(const uint8_t* d_boxes, size_t slot, const ui
     return hipGetLastError();
 }
 
-hipError_t launch_chacha_mask_accumulate_counted(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
-                                                 const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo, int64_t* d_acc_hi,
-                                                 RejectRecord* d_rejects, hipStream_t s) {
-    (void)mod;
-    if (max_seeds == 0 || dimension == 0) return hipSuccess;
-    const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
-    if (hipError_t e = grid_check(pos_blocks)) return e;
-    const uint64_t want_blocks = 256 * 8;                  // the split of launch_chacha_mask_accumulate, for the upper bound
-    uint64_t split = 1;
-    if (pos_blocks < want_blocks) split = ceil_div(want_blocks, pos_blocks);
-    if (split > max_seeds) split = max_seeds;
-    if (split > 65535) split = 65535;
-    const size_t per = ceil_div(max_seeds, split);
-    split = ceil_div(max_seeds, per);
-    chacha_mask_fast_counted_kernel<<<dim3((unsigned)pos_blocks, (unsigned)split), dim3(kThreads), 0, s>>>(
-        d_seeds, d_n_seeds, dimension, zone, d_acc_lo, d_acc_hi, d_rejects, per);
-    return hipGetLastError();
-}
-
 hipError_t launch_chacha_mask_plan(const RejectRecord* d_rejects, size_t n, uint32_t* d_plan, uint32_t* d_shift_list,
                                    uint32_t* d_exact_list, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -2481,69 +2415,68 @@ hipError_t launch_chacha_mask_plan(const RejectRecord* d_rejects, size_t n, uint
     return hipGetLastError();
 }
 
-// The list dimension of the grid is capped: about 4096 workgroups in all (an empty list costs that many that return after one
-// scalar load), never fewer than 16 list rows nor more than the list can hold
+// A list whose length the host knows gets one row of workgroups per entry, up to the grid limit.  For a length on the device the
+// list dimension of the grid is capped: about 4096 workgroups in all (an empty list costs that many that return after one scalar
+// load), never fewer than 16 list rows nor more than the list can hold
 hipError_t launch_chacha_mask_shift_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
                                            const RejectRecord* d_rejects, size_t dimension, uint64_t zone, uint64_t* d_acc_lo,
-                                           int64_t* d_acc_hi, hipStream_t s) {
+                                           int64_t* d_acc_hi, const MaskApply* apply, hipStream_t s) {
     if (max_list == 0 || dimension == 0) return hipSuccess;
+    if (max_list > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
     if (hipError_t e = grid_check(pos_blocks)) return e;
-    uint64_t gy = 4096 / pos_blocks;
-    if (gy < 16) gy = 16;
+    uint64_t gy;
+    if (d_n_list) {
+        gy = 4096 / pos_blocks;
+        if (gy < 16) gy = 16;
+        if (gy > max_list) gy = max_list;
+    } else {            // no caller today: the one driver plans every shift list on the device
+        gy = participants_per_launch(pos_blocks, max_list);
+    }
     if (gy > 65535) gy = 65535;
-    if (gy > max_list) gy = max_list;
-    chacha_mask_shift_listed_kernel<<<dim3((unsigned)pos_blocks, (unsigned)gy), dim3(kThreads), 0, s>>>(
-        d_seeds, d_list, d_n_list, d_rejects, dimension, zone, d_acc_lo, d_acc_hi);
+    const dim3 grid((unsigned)pos_blocks, (unsigned)gy);
+    if (apply)
+        chacha_mask_shift_listed_kernel<true><<<grid, dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, (uint32_t)max_list, d_rejects,
+                                                                              dimension, zone, nullptr, nullptr, *apply);
+    else
+        chacha_mask_shift_listed_kernel<false><<<grid, dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, (uint32_t)max_list, d_rejects,
+                                                                               dimension, zone, d_acc_lo, d_acc_hi, MaskApply{});
     return hipGetLastError();
 }
 
+// one workgroup per entry of a list whose length the host knows, up to the grid limit; at most 2048 for a length on the device
 hipError_t launch_chacha_mask_slow_listed(const uint32_t* d_seeds, const uint32_t* d_list, const uint32_t* d_n_list, size_t max_list,
                                           size_t dimension, const ModParams& mod, uint64_t zone, uint64_t* d_acc_lo,
-                                          int64_t* d_acc_hi, bool subtract_naive, hipStream_t s) {
+                                          int64_t* d_acc_hi, bool subtract_naive, const MaskApply* apply, hipStream_t s) {
     if (max_list == 0 || dimension == 0) return hipSuccess;
-    const unsigned grid = (unsigned)(max_list < 2048 ? max_list : 2048);
-    chacha_mask_slow_listed_kernel<<<dim3(grid), dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, dimension, mod, zone, d_acc_lo,
-                                                                         d_acc_hi, subtract_naive);
+    if (max_list > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t cap = d_n_list ? 2048 : kMaxBlocks;
+    const dim3 grid((unsigned)(max_list < cap ? max_list : cap));
+    if (apply)
+        chacha_mask_slow_listed_kernel<true><<<grid, dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, (uint32_t)max_list, dimension, mod,
+                                                                             zone, nullptr, nullptr, subtract_naive, *apply);
+    else
+        chacha_mask_slow_listed_kernel<false><<<grid, dim3(kThreads), 0, s>>>(d_seeds, d_list, d_n_list, (uint32_t)max_list, dimension,
+                                                                              mod, zone, d_acc_lo, d_acc_hi, subtract_naive, MaskApply{});
     return hipGetLastError();
 }
 
 // ---- masks applied to each participant's own vector (chacha.rs:24-54 for a device-resident tile) ------------------
-hipError_t launch_chacha_apply_fast(const uint32_t* d_seeds, size_t participants, size_t dimension, const ModParams& mod,
-                                    uint64_t zone, const int64_t* d_secrets, size_t secrets_stride, int64_t* d_out,
-                                    size_t out_stride, RejectRecord* d_rejects, hipStream_t s) {
+hipError_t launch_chacha_apply_fast(const uint32_t* d_seeds, size_t participants, size_t dimension, uint64_t zone,
+                                    const MaskApply& apply, RejectRecord* d_rejects, hipStream_t s) {
     if (participants == 0 || dimension == 0) return hipSuccess;
     const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
     if (hipError_t e = grid_check(pos_blocks)) return e;
     uint64_t per = 0xFFFFFFFFull / (pos_blocks * kThreads);
     if (per > 65535) per = 65535;
     if (per == 0) return hipErrorInvalidConfiguration;
+    // a slice's kernel counts participants from 0: keys, records and rows all move by p0, so record p stays participant p's
     for (size_t p0 = 0; p0 < participants; p0 += per) {
         const unsigned np = (unsigned)(participants - p0 < per ? participants - p0 : per);
-        const MaskApply ap{d_secrets + p0 * secrets_stride, secrets_stride, d_out + p0 * out_stride, out_stride, mod};
+        const MaskApply ap{apply.secrets + p0 * apply.secrets_stride, apply.secrets_stride, apply.out + p0 * apply.out_stride,
+                           apply.out_stride, apply.mod};
         chacha_mask_apply_kernel<<<dim3((unsigned)pos_blocks, np), dim3(kThreads), 0, s>>>(d_seeds + p0 * 8, dimension, zone,
                                                                                          d_rejects + p0, ap);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_chacha_apply_repair(const uint32_t* d_seeds, const uint32_t* d_shift_list, size_t n_shift,
-                                      const uint32_t* d_exact_list, size_t n_exact, const RejectRecord* d_rejects,
-                                      size_t dimension, const ModParams& mod, uint64_t zone, const int64_t* d_secrets,
-                                      size_t secrets_stride, int64_t* d_out, size_t out_stride, hipStream_t s) {
-    if (dimension == 0) return hipSuccess;
-    const MaskApply ap{d_secrets, secrets_stride, d_out, out_stride, mod};
-    const uint64_t pos_blocks = ceil_div(ceil_div(dimension, 8), kThreads);
-    if (hipError_t e = grid_check(pos_blocks)) return e;
-    for (size_t l0 = 0; l0 < n_shift; l0 += 65535) {
-        const unsigned nl = (unsigned)(n_shift - l0 < 65535 ? n_shift - l0 : 65535);
-        chacha_mask_shift_kernel<true><<<dim3((unsigned)pos_blocks, nl), dim3(kThreads), 0, s>>>(
-            d_seeds, d_shift_list + l0, d_rejects, dimension, zone, nullptr, nullptr, ap);
-    }
-    if (n_exact) {      // d_exact_list == nullptr: every participant 0..n_exact-1 in stream order
-        if (hipError_t e = grid_check(n_exact)) return e;
-        chacha_mask_slow_kernel<true><<<dim3((unsigned)n_exact), dim3(kThreads), 0, s>>>(d_seeds, d_exact_list, dimension, mod,
-                                                                                        zone, nullptr, nullptr, false, ap);
     }
     return hipGetLastError();
 }

@@ -833,6 +833,7 @@ def test_masked_participation_on_device(gpu, P, dim, pad):
                                           ((1 << 62) - (1 << 51), 1500, 120, 128),   # ~0.7 rejections per seed: shift + exact
                                           ((1 << 62) - (1 << 51), 40, 800, 256),     # rejections near the end: tail walk
                                           ((1 << 61) + 1, 8, 300, 128),              # 12 % rejection on 8 candidates
+                                          ((1 << 61) + 1, 8, 70000, 128),            # ... both repair lists at once, the shift list longer than its grid
                                           ((1 << 61) + 1, 3000, 4, 128)])            # rejections are the rule: exact order for all
 def test_chacha_masking_of_a_device_tile(gpu, q, dim, P, bits):
     """chacha.rs:24-54 for a device-resident tile: every participant gets an OS-entropy seed (returned as its mask,
@@ -857,6 +858,14 @@ def test_chacha_masking_of_a_device_tile(gpu, q, dim, P, bits):
     assert not seeds[:, nw:].any() and not masked[:, dim:].any()
     assert ((seeds[:, :nw] >= 0) & (seeds[:, :nw] < (1 << 32))).all()          # u32 words (chacha.rs:30-33)
     assert len({tuple(r) for r in seeds[:, :nw]}) == P                           # fresh entropy per participant
+    if P == 70000:
+        # the lists' lengths live on the device and their grids are bounded (4096 list rows at this dimension, 2048 exact-order
+        # workgroups): with ~45 000 seeds of 1..3 rejections the shift grid strides, and the ~790 with more run in the same call
+        from mask_combiner_cases import rejections
+        rejected, _ = rejections(seeds[:, :nw], q, dim)
+        n_shift, n_exact = int(((rejected >= 1) & (rejected <= 3)).sum()), int((rejected > 3).sum())
+        print(f"shift list {n_shift}, exact-order list {n_exact}")
+        assert n_shift > 4096 and n_exact > 16
     for p in range(P):
         mask = coracle.chacha_expand(seeds[p, :nw], q, dim)
         assert np.array_equal(masked[p, :dim], coracle.addsub(sec[p, :dim], mask, q)), p

@@ -7,7 +7,7 @@ rounds, REPS >= 20 timed):
     D  begin_dev + update_dev + finish_dev            seeds [P][4] resident in HBM, the combined mask stays there
     S  begin_dev + update_sealed_rows_dev + finish_dev   the same seeds as P sealed boxes resident in HBM
 Every run is a child process under its own time limit; a child that fails or runs out of time ends the whole measurement.
-    this tree: H D S            --parent-lib PATH: H again on a library built from the parent commit (it has no device form)
+    this tree: H D S            --parent-lib PATH: the same three legs on a library built from the parent commit, this tree / parent
 Writes mask_combine_dev.json / .txt into --out-dir (default profiles/r09).  SEEDS / DIMENSION / REPS override the shape."""
 import argparse
 import ctypes as C
@@ -20,17 +20,12 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 P62 = 4611686006577364993
-NEW = ["sda_mask_combiner_begin_dev", "sda_mask_combiner_update_dev", "sda_mask_combiner_update_sealed_rows_dev",
-       "sda_mask_combiner_finish_dev"]
 
 
 def child(legs):
     import numpy as np
     from sda_amd import capi, crypto
     from sda_amd.device import DeviceBuffer, DeviceBytes, synchronize
-    if legs == "H":
-        for name in NEW:
-            capi.SIGNATURES.pop(name, None)                  # a library built from the parent commit does not have them
     lib = capi.load()
     P, dim, reps = int(os.environ.get("SEEDS", "4096")), int(os.environ.get("DIMENSION", str(1 << 20))), max(20, int(os.environ.get("REPS", "20")))
     S = np.random.default_rng(P).integers(0, 1 << 32, size=(P, 4), dtype=np.int64)
@@ -106,7 +101,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--legs", default="HDS")
-    ap.add_argument("--parent-lib", default=None, help="libsda_hip.so built from the parent commit: leg H on it")
+    ap.add_argument("--parent-lib", default=None, help="libsda_hip.so built from the parent commit: the same legs on it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "r09"))
     ap.add_argument("--limit", type=int, default=240, help="seconds per child process")
     a = ap.parse_args()
@@ -122,7 +117,7 @@ def main():
             f.write(report(res))
     save()
     if a.parent_lib:
-        res["parent_commit"] = run_child(["--legs", "H"], {"SDA_HIP_LIBRARY": os.path.abspath(a.parent_lib)}, a.limit)
+        res["parent_commit"] = run_child(["--legs", "HDS"], {"SDA_HIP_LIBRARY": os.path.abspath(a.parent_lib)}, a.limit)
         save()
     print(report(res))
 
@@ -139,10 +134,10 @@ def report(res):
         if r.get("kernels_of_S"):
             lines.append(f"  S ran: {r['kernels_of_S']}")
     if "parent_commit" in res:
-        p = res["parent_commit"]["legs"]["H"]["median_ms"]
-        lines += ["", f"D (this tree) / H (parent commit) = {t['legs']['D']['median_ms'] / p:.3f}   (required: <= 1.04)",
-                  f"S (this tree) / H (parent commit) = {t['legs']['S']['median_ms'] / p:.3f}",
-                  f"H (this tree) / H (parent commit) = {t['legs']['H']['median_ms'] / p:.3f}"]
+        lines.append("")
+        for k, v in res["parent_commit"]["legs"].items():
+            lines.append(f"{k}: this tree / parent commit = {t['legs'][k]['median_ms'] / v['median_ms']:.3f}")
+        lines.append("required: every ratio <= 1.04, or the parent-vs-parent spread of the day where that is larger")
     return "\n".join(lines) + "\n"
 
 

@@ -56,7 +56,7 @@ for P in (256, 4096):
     mc = crypto.MaskCombiner(crypto.ChaCha(P62, dim, 128))
     dt = timed(lambda: mc.combine(seeds), reps=3)
     out[f"chacha_mask_combine_P{P}_dim1Mi"] = {"ms": dt * 1e3, "masks_per_s": P * dim / dt,
-                                               "note": "host call: includes seed upload, flag readback, 8 MB result download"}
+                                               "note": "host call: includes seed upload, 8 MB result download"}
 
 # M1: full masking with the device CSPRNG, dim 16 Mi (host buffers: PCIe included)
 dim = 1 << 24
