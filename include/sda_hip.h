@@ -445,7 +445,10 @@ int sda_secret_masker_mask(sda_secret_masker_t* m,
  * OS-entropy seed per participant (chacha.rs:29-33), its ceil(seed_bitsize/32) words written to d_masks[p][..]
  * (the "mask" a participant sends is its seed, chacha.rs:48-50; mask_stride >= that many), masked[p][i] =
  * (secrets[p][i] + i-th rand-0.3 ChaChaRng gen_range value of that seed) mod q; len must equal the scheme's dimension
- * (SDA_ERR_ASSERTION, chacha.rs:26); the call synchronises `stream`.  Full masks are combined on the recipient side
+ * (SDA_ERR_ASSERTION, chacha.rs:26); the call synchronises `stream`.  IN PLACE: Full and None may be called with d_masked ==
+ * d_secrets; the ChaCha kind may not - a mask that the rejection repair moves is applied to secrets[p][i] a second time - and
+ * answers SDA_ERR_INVALID_ARGUMENT, before anything is written, when the two ranges (participants rows of len words at their
+ * strides) overlap anywhere.  Full masks are combined on the recipient side
  * exactly like shares (full.rs:37-52 == combiner.rs:15-29).  Either kind of mask stays on the device for the recipient:
  * d_masks rows (Full mask vectors, ChaCha seeds) go to sda_mask_combiner_update_dev, their sealed boxes to
  * sda_mask_combiner_update_sealed_rows_dev; sda_mask_combiner_combine is the host form of the same sums. */

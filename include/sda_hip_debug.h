@@ -84,6 +84,21 @@ int  sda_debug_mem_info(size_t* free_bytes, size_t* total_bytes);
  * a row).  The sealed-box ABI cannot do this: there r and s come out of Salsa20.  Synchronous; for tests/test_sealedbox_extremes_gpu.py. */
 int  sda_debug_poly1305_rows_dev(const unsigned char* keys, const unsigned char* d_msgs, size_t msg_slot,
                                  const unsigned long long* d_msg_bytes, size_t rows, size_t max_msg_bytes, unsigned char* tags);
+/* The ChaCha kind of sda_secret_masker_mask_batch_dev (include/sda_hip.h: same arguments, same checks, same code) with the seeds
+ * taken from the HOST array seed_words - [participants][ceil(seed_bitsize / 32)] 32-bit words - and not from the OS: the only way
+ * to put a chosen seed through the per-participant (APPLY) instances of the rejection repair.  Another kind of masker answers
+ * SDA_ERR_INVALID_ARGUMENT.  For tests/test_chacha_repair_gpu.py. */
+struct sda_secret_masker;
+int  sda_debug_secret_masker_mask_batch_seeded_dev(struct sda_secret_masker* m, const unsigned* seed_words, const long long* d_secrets,
+                                                   size_t participants, size_t len, size_t secrets_stride,
+                                                   unsigned long long first_participant, long long* d_masks, size_t mask_stride,
+                                                   long long* d_masked, size_t masked_stride, void* stream);
+/* The repair plan of the last chunk the rand-0.3 ChaCha mask driver (chacha_expand) ran on this thread, whichever entry point
+ * called it: out = { 1 if (modulus, dimension) sent every key to the exact-order walk else 0, length of the shift list, length of
+ * the exact-order list, keys expanded (for sealed rows: the rows that passed) }.  The query waits for the call's stream and reads
+ * the plan head; the driver itself never waits, in either library.  The handle that made the call must still be alive.
+ * SDA_ERR_STATE before the first expansion. */
+int  sda_debug_last_mask_plan(unsigned out[4]);
 struct sda_sharing_scheme;
 int  sda_debug_select_path(const struct sda_sharing_scheme* scheme, const char* knobs, char* out, size_t cap);
 #ifdef __cplusplus

@@ -247,6 +247,10 @@ HOOK_SIGNATURES = {
     "sda_debug_select_path": (C.c_int, [_SS, C.c_char_p, C.c_char_p, C.c_size_t]),
     "sda_debug_last_reveal_kernel": (C.c_char_p, []),
     "sda_debug_poly1305_rows_dev": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_char_p]),
+    "sda_debug_secret_masker_mask_batch_seeded_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                                C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                                C.c_void_p]),
+    "sda_debug_last_mask_plan": (C.c_int, [C.POINTER(C.c_uint * 4)]),
 }
 
 _loaded = {}          # path -> CDLL with signatures attached

@@ -2013,6 +2013,17 @@ struct MaskCore {
 // ---- the rand-0.3 ChaCha mask expansion (chacha.rs:36-39, :60-73): one driver for every entry point ----
 // head of the plan scratch (MaskCore::d_list): three counters the kernels keep, then the two lists of a chunk
 enum { PLAN_SHIFT = 0, PLAN_EXACT = 1, PLAN_KEYS = 2, PLAN_HEAD = 4 };
+#ifdef SDA_TEST_HOOKS
+// where the plan head of the last chacha_expand chunk on this thread lives, and what the host decided for it
+struct LastMaskPlan {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    const uint32_t* head = nullptr;
+    uint32_t keys = 0;
+    bool counted = false, all_exact = false;
+};
+thread_local LastMaskPlan g_last_mask_plan;
+#endif
 constexpr size_t kMaskChunk = (size_t)1 << 20;             // keys per run of the driver when the caller can split them
 
 // room for ns keys in c.d_seeds and for their repair plan, the plan's counters zeroed
@@ -2045,7 +2056,11 @@ int chacha_expand(MaskCore& c, size_t ns, bool counted, size_t dimension, const 
     const uint32_t* n_keys = counted ? plan + PLAN_KEYS : nullptr;
     uint64_t* lo = c.acc.lo.as<uint64_t>();
     int64_t* hi = c.acc.hi.as<int64_t>();
-    if (chacha_exact_order_for_all(zone, dimension)) {
+    const bool all_exact = chacha_exact_order_for_all(zone, dimension);
+#ifdef SDA_TEST_HOOKS
+    g_last_mask_plan = {c.ctx.device, s, plan, (uint32_t)ns, counted, all_exact};     // read by sda_debug_last_mask_plan, which waits
+#endif
+    if (all_exact) {
         HIP_TRY(launch_chacha_mask_slow_listed(keys, nullptr, n_keys, ns, dimension, c.mod, zone, lo, hi, false, apply, s));
         return SDA_OK;
     }
@@ -2085,6 +2100,23 @@ int end_synchronised(hipStream_t s, Enqueue&& enqueue) {
     return SDA_OK;
 }
 }  // namespace
+
+#ifdef SDA_TEST_HOOKS
+extern "C" int sda_debug_last_mask_plan(unsigned out[4]) {
+    if (!out) return fail(SDA_ERR_INVALID_ARGUMENT, "out is NULL");
+    const LastMaskPlan& l = g_last_mask_plan;
+    if (!l.head) return fail(SDA_ERR_STATE, "no ChaCha mask expansion has run on this thread");
+    uint32_t head[PLAN_HEAD];
+    HIP_TRY(hipSetDevice(l.device));
+    HIP_TRY(hipStreamSynchronize(l.stream));
+    HIP_TRY(hipMemcpy(head, l.head, sizeof head, hipMemcpyDeviceToHost));
+    out[0] = l.all_exact ? 1u : 0u;
+    out[1] = head[PLAN_SHIFT];
+    out[2] = head[PLAN_EXACT];
+    out[3] = l.counted ? head[PLAN_KEYS] : l.keys;
+    return SDA_OK;
+}
+#endif
 
 struct sda_secret_masker { MaskCore core; };
 struct sda_mask_combiner { MaskCore core; };
@@ -2224,11 +2256,11 @@ extern "C" int sda_secret_masker_mask(sda_secret_masker_t* m, const int64_t* sec
     return SDA_OK;
 }
 
-// device-resident batch of participants (participate.rs:52-54 for a whole tile): Full and None schemes
-extern "C" int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const int64_t* d_secrets, size_t participants,
-                                                size_t len, size_t secrets_stride, uint64_t first_participant,
-                                                int64_t* d_masks, size_t mask_stride, int64_t* d_masked,
-                                                size_t masked_stride, void* stream) {
+// device-resident batch of participants (participate.rs:52-54 for a whole tile), every scheme.  seed_words: the ChaCha seeds,
+// host [participants][seed words] - the test hook's; nullptr (every release caller) draws them from the OS
+static int mask_batch_dev(sda_secret_masker_t* m, const uint32_t* seed_words, const int64_t* d_secrets, size_t participants,
+                          size_t len, size_t secrets_stride, uint64_t first_participant, int64_t* d_masks, size_t mask_stride,
+                          int64_t* d_masked, size_t masked_stride, void* stream) {
     if (!m) return fail(SDA_ERR_INVALID_ARGUMENT, "masker is NULL");
     MaskCore& c = m->core;
     if (c.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "SDA_VALUES_RUST_SIGNED is served by the trait-shaped mask(); the batched device form emits canonical residues");
@@ -2241,11 +2273,18 @@ extern "C" int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const in
                         (unsigned long long)c.scheme.dimension, len);
         const size_t nw = c.seed_words();
         if (!d_masks || mask_stride < nw) return fail(SDA_ERR_INVALID_ARGUMENT, "d_masks must hold %zu seed words per participant", nw);
+        // a repair writes a position a second time from secrets[p][i]: in place it would add a second mask to the first.  Refused
+        // for every (modulus, dimension), also where no repair can happen, so that the rule does not depend on the plan
+        const uintptr_t sec0 = reinterpret_cast<uintptr_t>(d_secrets), out0 = reinterpret_cast<uintptr_t>(d_masked);
+        const uintptr_t sec1 = sec0 + ((participants - 1) * secrets_stride + len) * 8, out1 = out0 + ((participants - 1) * masked_stride + len) * 8;
+        if (sec0 < out1 && out0 < sec1)
+            return fail(SDA_ERR_INVALID_ARGUMENT, "d_masked overlaps d_secrets: the ChaCha kind does not mask in place");
         SDA_TRY(c.ctx.use());
         hipStream_t s = c.ctx.pick(stream);
         // one OS-entropy seed per participant (chacha.rs:29-33); the "mask" a participant sends is its seed (chacha.rs:48-50)
         WipedVec<uint32_t> raw(participants * nw ? participants * nw : 1);
-        SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
+        if (seed_words) memcpy(raw.data(), seed_words, participants * nw * 4);
+        else SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
         WipedVec<int64_t> words(participants * nw);
         WipedVec<uint32_t> key8(participants * 8, 0u);
         for (size_t p = 0; p < participants; ++p)
@@ -2277,6 +2316,26 @@ extern "C" int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const in
     HIP_TRY(he);
     return SDA_OK;
 }
+
+extern "C" int sda_secret_masker_mask_batch_dev(sda_secret_masker_t* m, const int64_t* d_secrets, size_t participants,
+                                                size_t len, size_t secrets_stride, uint64_t first_participant,
+                                                int64_t* d_masks, size_t mask_stride, int64_t* d_masked,
+                                                size_t masked_stride, void* stream) {
+    return mask_batch_dev(m, nullptr, d_secrets, participants, len, secrets_stride, first_participant, d_masks, mask_stride, d_masked,
+                          masked_stride, stream);
+}
+#ifdef SDA_TEST_HOOKS
+// the ChaCha kind of the call above with chosen seeds: the repair lists of the APPLY kernels cannot be reached on purpose otherwise
+extern "C" int sda_debug_secret_masker_mask_batch_seeded_dev(sda_secret_masker_t* m, const unsigned* seed_words, const int64_t* d_secrets,
+                                                             size_t participants, size_t len, size_t secrets_stride,
+                                                             uint64_t first_participant, int64_t* d_masks, size_t mask_stride,
+                                                             int64_t* d_masked, size_t masked_stride, void* stream) {
+    if (!m || !seed_words) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m->core.scheme.kind != SDA_MASKING_CHACHA) return fail(SDA_ERR_INVALID_ARGUMENT, "only the ChaCha kind takes seeds");
+    return mask_batch_dev(m, seed_words, d_secrets, participants, len, secrets_stride, first_participant, d_masks, mask_stride, d_masked,
+                          masked_stride, stream);
+}
+#endif
 
 extern "C" int sda_mask_combiner_combine(sda_mask_combiner_t* mc, const int64_t* const* rows, const size_t* row_lens,
                                          size_t n_rows, int64_t* out, size_t out_cap, size_t* out_len) {
