@@ -753,6 +753,42 @@ int sda_base64_encode_rows_dev(const uint8_t* d_in, size_t in_slot, const uint64
  *                   serve it).  Ephemeral secrets are uploaded, used and wiped as in seal_rows_dev.  Uses the sealed-box handle's
  *                   scratch and the codec's: the one-stream-at-a-time rule holds for both.
  *
+ *   sda_secret_masker_mask_sealed_rows_dev : participate.rs:52-72 in one call - the secrets of `participants` participants are masked
+ *                   and each participant's mask is sealed to the recipient's key pk (its recipient_encryption).  Row p is the box
+ *                   of participant p at d_boxes + p * slot_bytes, d_row_bytes[p] = payload bytes + 48: the slotted layout
+ *                   sda_mask_combiner_update_sealed_rows_dev and open_rows_dev take.  d_masked[p][i] is what
+ *                   sda_secret_masker_mask_batch_dev writes.  esk: NULL = OS entropy, else participants * 32 bytes, TESTS ONLY.
+ *                   Full (full.rs:21-35): masks[p][i] is the sda-drbg-v1 draw of stream first_participant + p under the handle's
+ *                   key, round count and draw rule, exactly the draw of mask_batch_dev; in production mode the call runs under a
+ *                   call key of its own, like mask_batch_dev.  Box and length are byte for byte what mask_batch_dev followed by
+ *                   sda_sealedbox_seal_share_rows_dev (n_pks = 1, rows_per_key = rows = participants, len = row_stride = len)
+ *                   write under the same key and ephemeral secrets, and d_masked is bit for bit mask_batch_dev's.  After the
+ *                   setup pass ONE kernel, one wave per participant, draws the row's masks, adds them onto the secrets it has
+ *                   loaded, stores the masked secrets, and encodes and encrypts the masks while they are in registers and LDS; the
+ *                   Poly1305 pass over the ciphertext stores the tags.  No mask value and no plaintext varint byte is written to
+ *                   device memory: there is no mask buffer and no wire buffer.  d_masked == d_secrets with equal strides is allowed
+ *                   (each element is read and written once, by the same lane).  len == 0 gives `participants` 48-byte boxes of
+ *                   the empty message and writes nothing to d_masked.  A single very long row is one wave's work: the call is made
+ *                   for many participants.
+ *                   ChaCha (chacha.rs:24-54): one OS-entropy seed per participant; the mask a participant sends is its seed
+ *                   words, each `as i64`, and the box is byte for byte what seal_share_rows_dev writes for those words.  d_masked
+ *                   is what mask_batch_dev writes for those seeds (the same expansion driver, rejection repair included).  The
+ *                   seed rows live in scratch of the masker - grown wiped, zeroed before the call returns, wiped on free, never
+ *                   caller-visible and never copied back.  len != scheme.dimension -> SDA_ERR_ASSERTION; d_masked overlapping
+ *                   d_secrets -> SDA_ERR_INVALID_ARGUMENT, as mask_batch_dev.  Like mask_batch_dev this kind synchronises the
+ *                   stream.
+ *                   None -> SDA_ERR_UNSUPPORTED (participate.rs:56-57 sends no recipient encryption: call mask_batch_dev);
+ *                   SDA_VALUES_RUST_SIGNED -> SDA_ERR_UNSUPPORTED, as mask_batch_dev.
+ *                   A recipient key of small order refuses every row exactly as seal_share_rows_dev does: d_row_bytes[p] = 0, the
+ *                   epk written, nothing past byte 32 of the slot touched - CHECK d_row_bytes BEFORE USING d_masked.  Full leaves
+ *                   the masked rows exactly as passed; ChaCha writes them as mask_batch_dev does (the expansion does not read the
+ *                   box state).  SDA_ERR_INVALID_ARGUMENT before any launch or write for: a NULL handle or pointer (d_secrets /
+ *                   d_masked may be NULL only when len == 0), secrets_stride < len or masked_stride < len, slot_bytes not a
+ *                   multiple of 16 or below sda_varint_slot_size(sda_secret_masker_mask_len(m, len)) + 48, d_boxes not 16-byte
+ *                   aligned, the three handles not on one device, Full stream ids at or above 2^56.  participants == 0 returns
+ *                   SDA_OK and writes nothing.  Ephemeral secrets are uploaded, used and wiped as in seal_rows_dev.  Uses the
+ *                   sealed-box handle's scratch: the one-stream-at-a-time rule holds.
+ *
  *   sda_mask_combiner_update_sealed_rows_dev : receive.rs:101-118 from the participants' sealed mask encryptions - an update
  *                   form of the mask combiner's device job (sda_mask_combiner_begin_dev above), rows laid out as for
  *                   open_rows_dev.  Step 1 verifies every tag exactly as open_rows_dev does (d_ok[r] when d_ok is given;
@@ -824,6 +860,13 @@ int  sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c, sda_vari
                                                const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
                                                uint32_t* d_ok /* optional */, uint32_t* d_status, void* stream);
+/* participate.rs:52-72: the secrets masked, every participant's mask sealed to the recipient (see above) */
+int  sda_secret_masker_mask_sealed_rows_dev(sda_secret_masker_t* m, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                            const uint8_t pk[32] /* the recipient's key */,
+                                            const uint8_t* esk /* NULL = OS entropy; else participants*32, tests only */,
+                                            const int64_t* d_secrets, size_t participants, size_t len, size_t secrets_stride,
+                                            uint64_t first_participant, int64_t* d_masked, size_t masked_stride, uint8_t* d_boxes,
+                                            size_t slot_bytes, uint64_t* d_row_bytes, void* stream);
 /* receive.rs:101-118: the participants' sealed mask encryptions summed into the mask combiner's device job (see above) */
 int  sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* c, sda_varint_codec_t* codec, sda_sealedbox_t* b,
                                               const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,

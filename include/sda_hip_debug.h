@@ -93,6 +93,19 @@ int  sda_debug_secret_masker_mask_batch_seeded_dev(struct sda_secret_masker* m, 
                                                    size_t participants, size_t len, size_t secrets_stride,
                                                    unsigned long long first_participant, long long* d_masks, size_t mask_stride,
                                                    long long* d_masked, size_t masked_stride, void* stream);
+/* The ChaCha kind of sda_secret_masker_mask_sealed_rows_dev (include/sda_hip.h: same arguments, same checks, same code) with the
+ * seeds taken from the HOST array seed_words, as the hook above: the only way to know which seed rows the boxes must hold and which
+ * repair plan the masked secrets went through.  Another kind of masker answers SDA_ERR_INVALID_ARGUMENT.  For
+ * tests/test_mask_sealed_gpu.py. */
+struct sda_varint_codec;
+struct sda_sealedbox;
+int  sda_debug_secret_masker_mask_sealed_rows_seeded_dev(struct sda_secret_masker* m, const unsigned* seed_words,
+                                                         struct sda_varint_codec* codec, struct sda_sealedbox* b,
+                                                         const unsigned char pk[32], const unsigned char* esk, const long long* d_secrets,
+                                                         size_t participants, size_t len, size_t secrets_stride,
+                                                         unsigned long long first_participant, long long* d_masked, size_t masked_stride,
+                                                         unsigned char* d_boxes, size_t slot_bytes, unsigned long long* d_row_bytes,
+                                                         void* stream);
 /* The repair plan of the last chunk the rand-0.3 ChaCha mask driver (chacha_expand) ran on this thread, whichever entry point
  * called it: out = { 1 if (modulus, dimension) sent every key to the exact-order walk else 0, length of the shift list, length of
  * the exact-order list, keys expanded (for sealed rows: the rows that passed) }.  The query waits for the call's stream and reads

@@ -200,6 +200,9 @@ SIGNATURES = {
                                                     C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_share_generator_generate_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                                                C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sda_secret_masker_mask_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                         C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p]),
     "sda_share_combiner_update_sealed_rows_dev": (C.c_int, [_H, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
                                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                             C.c_void_p]),
@@ -250,6 +253,9 @@ HOOK_SIGNATURES = {
     "sda_debug_secret_masker_mask_batch_seeded_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                                                 C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                                 C.c_void_p]),
+    "sda_debug_secret_masker_mask_sealed_rows_seeded_dev": (C.c_int, [_H, C.c_void_p, _H, _H, C.c_char_p, C.c_char_p, C.c_void_p,
+                                                                      C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p,
+                                                                      C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_debug_last_mask_plan": (C.c_int, [C.POINTER(C.c_uint * 4)]),
 }
 

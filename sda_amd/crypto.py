@@ -536,6 +536,18 @@ class SecretMasker(_Handle):
                                                          first_participant, d_masks or None, mask_stride, d_masked,
                                                          masked_stride, stream or None))
 
+    def mask_sealed_rows_dev(self, codec: "VarintCodec", box: "SealedBox", recipient_pk: bytes, d_secrets: int, participants: int,
+                             length: int, secrets_stride: int, d_masked: int, masked_stride: int, d_boxes: int, slot_bytes: int,
+                             d_row_bytes: int, first_participant: int = 0, esk: Optional[bytes] = None, stream: int = 0) -> None:
+        """participate.rs:52-72 for a device-resident tile: the masked secrets to d_masked, participant p's mask sealed to the
+        recipient into d_boxes + p * slot_bytes, d_row_bytes[p] = payload + 48 (0: refused - check it before using d_masked).
+        Full: no mask and no plaintext varint reaches device memory.  ChaCha: the sealed mask is the participant's seed.
+        None has no recipient encryption (SDA_ERR_UNSUPPORTED: mask_batch_dev).  esk injects participants*32 bytes (tests only)."""
+        assert len(recipient_pk) == 32 and (esk is None or len(esk) == 32 * participants)
+        check(self._lib.sda_secret_masker_mask_sealed_rows_dev(
+            self._h, codec._h, box._h, recipient_pk, esk, d_secrets or None, participants, length, secrets_stride, first_participant,
+            d_masked or None, masked_stride, d_boxes, slot_bytes, d_row_bytes, stream or None))
+
 
 class MaskCombiner(_Handle):
     """masking/mod.rs:21-23; impl none.rs:21-26, full.rs:37-52, chacha.rs:56-77."""
@@ -703,6 +715,57 @@ def full_aggregation(aggregation: Aggregation, inputs: Sequence[Sequence[int]], 
     return {"masks": masks, "masked": maskeds, "shares": shares, "clerk_sums": clerk_sums,
             "combined_mask": mask, "masked_output": masked_output, "output": output,
             "positive": RecipientOutput(a.modulus, output).positive().values}
+
+
+def participate_sealed(aggregation: Aggregation, secrets_2d, recipient_pk: bytes, clerk_pks: Sequence[bytes],
+                       first_participant: int = 0, mask_esk: Optional[bytes] = None, share_esk: Optional[bytes] = None):
+    """new_participation (participate.rs:37-113) for a tile of P participants, from the secrets to wire bytes in two device
+    calls: SecretMasker.mask_sealed_rows_dev (masked secrets, which stay on the device, and the P sealed masks), then
+    ShareGenerator.generate_sealed_rows_dev on the masked secrets.  Returns (mask_job, clerk_jobs): the SDAJOBv1 SEALED blob
+    of the P mask boxes - the argument of MaskCombiner.combine_sealed_job; None for NoMask, whose secrets are shared as they
+    are (participate.rs:56-57) - and the n blobs of P share boxes each, clerk c's being the argument of
+    ShareCombiner.clerk_sealed_job.  A sharing shape generate_sealed_rows_dev refuses raises its error unchanged.
+    mask_esk / share_esk inject P*32 / n*P*32 bytes of ephemeral secrets (tests only)."""
+    from .device import DeviceBuffer, DeviceBytes
+    a = aggregation
+    m = np.ascontiguousarray(secrets_2d, dtype=np.int64)
+    if m.ndim != 2:
+        raise ValueError("participate_sealed takes a matrix: one participant's secrets per row")
+    P, length = m.shape
+    if length != a.vector_dimension:
+        raise ValueError("The input length does not match the aggregation.")             # participate.rs:44-46
+    n = a.committee_sharing_scheme.output_size()
+    if len(clerk_pks) != n:
+        raise ValueError(f"one key per clerk: {n} keys, got {len(clerk_pks)}")
+    codec, box = VarintCodec(), SealedBox()
+    d_secrets = DeviceBuffer.from_numpy(m) if m.size else None
+    d_ptr = d_secrets.ptr if m.size else 0
+
+    def jobs_of(d_boxes, d_lens, slot, groups):
+        """`groups` SDAJOBv1 SEALED blobs of P rows each out of the slotted rows of a device call"""
+        lens = np.frombuffer(d_lens.to_bytes(groups * P * 8), dtype="<u8")
+        if (lens == 0).any():
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, "sealing refused: a public key is a small-order point (all-zero shared secret)")
+        raw = d_boxes.to_bytes(groups * P * slot)
+        return [bytes(JobContainer.build(capi.JOB_SEALED, [raw[r * slot:r * slot + int(lens[r])] for r in range(g * P, (g + 1) * P)]))
+                for g in range(groups)]
+
+    mask_job = None
+    if a.masking_scheme.has_mask():
+        masker = SecretMasker(a.masking_scheme)
+        slot = codec.slot_size(int(masker._lib.sda_secret_masker_mask_len(masker._h, length))) + SealedBox.SEALBYTES
+        d_boxes, d_lens = DeviceBytes(max(P * slot, 16)), DeviceBytes(max(P * 8, 8)).zero()
+        d_masked = DeviceBuffer(max(m.size, 2))
+        masker.mask_sealed_rows_dev(codec, box, recipient_pk, d_ptr, P, length, length, d_masked.ptr if m.size else 0, length,
+                                    d_boxes.ptr, slot, d_lens.ptr, first_participant, mask_esk)
+        mask_job = jobs_of(d_boxes, d_lens, slot, 1)[0] if P else bytes(JobContainer.build(capi.JOB_SEALED, []))
+        d_ptr = d_masked.ptr if m.size else 0
+    generator = ShareGenerator(a.committee_sharing_scheme)
+    slot = codec.slot_size(generator.batch_count(length)) + SealedBox.SEALBYTES
+    d_boxes, d_lens = DeviceBytes(max(n * P * slot, 16)), DeviceBytes(max(n * P * 8, 8)).zero()
+    generator.generate_sealed_rows_dev(codec, box, clerk_pks, d_ptr, P, length, length, d_boxes.ptr, slot, d_lens.ptr,
+                                       first_participant, share_esk)
+    return mask_job, jobs_of(d_boxes, d_lens, slot, n)
 
 
 # ---- share-vector wire codec (SURVEY.md 8f rank 1) -------------------------------------------------------------

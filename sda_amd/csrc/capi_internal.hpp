@@ -21,6 +21,10 @@ int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t 
 // secrets inside the encode pass (launch_share_seal_stream); n keys, rows_per_key = participants
 int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, const uint8_t* esk, const sda::ShareJob& J, int rounds,
                                        uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
+// sda_secret_masker_mask_sealed_rows_dev (Full) after its argument checks: the same sequence with the rows drawn inside the encode
+// pass, which also stores the masked secrets (launch_mask_seal_stream); one key, rows = J.participants
+int capi_sealedbox_seal_masked_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const sda::MaskJob& J, int rounds,
+                                    uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
 // sda_share_combiner_finish_sealed_rows_dev after its argument checks: the same sequence with the rows computed from the clerk
 // sums S and every row split over the chip (launch_sum_lengths, launch_scan_u32, launch_sum_seal_wide); one key, rows = S.jobs.
 // The scan scratch is the caller's (the codec handle's): d_block_bytes and d_block_off hold S.jobs * sum_seal_blocks(S.len) entries

@@ -381,6 +381,21 @@ struct ShareJob {
 };
 hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
                                     uint64_t* d_msg_bytes, hipStream_t s);
+// secrets -> masked secrets in memory and the ciphertext of the participants' sealed mask rows in one pass (participate.rs:52-72,
+// full.rs:21-35): row p's masks are the sda-drbg-v1 draws of stream first_participant + p (launch_full_mask_drbg's), drawn by the
+// wave that adds them onto the secrets, encodes and encrypts them; no mask reaches memory.  masked == secrets with equal strides
+// is allowed.  States (one key, rows_per_key = participants), box layout and d_msg_bytes as launch_varint_seal_stream; a row whose
+// state says `bad` is left alone, its masked row too
+struct MaskJob {
+    const int64_t* secrets;  size_t secrets_stride;   // participant p at secrets + p * secrets_stride
+    int64_t* masked;         size_t masked_stride;
+    size_t len, participants;                         // values per row = secrets per participant
+    uint64_t first_participant;
+    ModParams mod;
+    DrbgKey key;
+};
+hipError_t launch_mask_seal_stream(const MaskJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                   uint64_t* d_msg_bytes, hipStream_t s);
 // clerk sums -> the ciphertext of the sealed clerking results, every row split over the chip (clerk.rs:84-100): job j's `len`
 // 128-bit sums are folded mod m, encoded and encrypted into d_boxes + j * slot_bytes + 48 under d_states[j], in blocks of 2048
 // values (sum_seal_blocks(len) per job, one workgroup each).  launch_sum_lengths writes the blocks' byte counts

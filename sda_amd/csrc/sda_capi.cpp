@@ -1972,6 +1972,7 @@ struct MaskCore {
     Ctx ctx;
     AccState acc;
     DevBuf tile, d_a, d_b, d_out, d_seeds, d_flags, d_list;
+    DevBuf d_words;                // mask_sealed_rows_dev, ChaCha: the participants' seed rows while they are sealed - never caller-visible
     Drbg drbg;
     bool rust_signed = false;      // SDA_VALUES_RUST_SIGNED: full.rs:30,46-48,62 / chacha.rs:43,88 with Rust's own `%`
     bool begun = false;            // the combiner's device job (begin_dev .. finish_dev) and its dimension
@@ -2003,7 +2004,7 @@ struct MaskCore {
     void destroy() {
         if (ctx.device >= 0) (void)hipSetDevice(ctx.device);
         acc.release(); tile.wipe_release(); d_a.wipe_release(); d_b.wipe_release(); d_out.wipe_release();
-        d_seeds.wipe_release(); d_flags.release(); d_list.release();
+        d_seeds.wipe_release(); d_words.wipe_release(); d_flags.release(); d_list.release();
         ctx.destroy();
         drbg.wipe();
     }
@@ -2905,6 +2906,118 @@ extern "C" int sda_share_generator_generate_sealed_rows_dev(sda_share_generator_
     snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
     return SDA_OK;
 }
+
+// participate.rs:52-72 for a tile of participants: the secrets masked on the device and the mask sealed to the recipient, in one call.
+// Full: setup, ONE pass that draws a row's masks, stores the masked secrets, encodes and encrypts the masks, tags - no mask reaches
+// memory.  ChaCha: the mask a participant sends is its seed, so the driver of mask_batch_dev expands the seeds onto the secrets and
+// the seed rows are sealed from scratch of the masker.  seed_words: the ChaCha seeds, host [participants][seed words] - the test
+// hook's; nullptr (every release caller) draws them from the OS
+static int mask_sealed_rows_dev(sda_secret_masker_t* m, const uint32_t* seed_words, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                const uint8_t pk[32], const uint8_t* esk, const int64_t* d_secrets, size_t participants, size_t len,
+                                size_t secrets_stride, uint64_t first_participant, int64_t* d_masked, size_t masked_stride,
+                                uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, void* stream) {
+    if (!m || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    MaskCore& c = m->core;
+    if (c.scheme.kind == SDA_MASKING_NONE)
+        return fail(SDA_ERR_UNSUPPORTED, "the None scheme sends no recipient encryption (participate.rs:56-57): call sda_secret_masker_mask_batch_dev");
+    if (c.rust_signed)
+        return fail(SDA_ERR_UNSUPPORTED, "SDA_VALUES_RUST_SIGNED is served by the trait-shaped mask(); the batched device forms (mask_batch_dev, mask_sealed_rows_dev) emit canonical residues");
+    if (!pk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL recipient key");
+    if (!d_boxes || !d_row_bytes || (len > 0 && (!d_secrets || !d_masked))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    if (secrets_stride < len || masked_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "stride < len");
+    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    const size_t mask_len = (size_t)sda_secret_masker_mask_len(m, len);
+    if (mask_len > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(mask_len) + SDA_SEALBYTES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(sda_secret_masker_mask_len(len)) + 48");
+    if (capi_sealedbox_device(b) != codec->ctx.device || c.ctx.device != codec->ctx.device)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the masker lives on device %d, the sealed-box handle on device %d, the codec on device %d",
+                    c.ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    if (c.scheme.kind == SDA_MASKING_CHACHA) {                                // chacha.rs:24-54 for every participant
+        if (len != c.scheme.dimension)
+            return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (dimension %llu, secrets %zu) - chacha.rs:26",
+                        (unsigned long long)c.scheme.dimension, len);
+        if (participants == 0) return SDA_OK;
+        if (len) {                                                            // as mask_batch_dev: a repair writes a position a second time
+            const uintptr_t sec0 = reinterpret_cast<uintptr_t>(d_secrets), out0 = reinterpret_cast<uintptr_t>(d_masked);
+            const uintptr_t sec1 = sec0 + ((participants - 1) * secrets_stride + len) * 8, out1 = out0 + ((participants - 1) * masked_stride + len) * 8;
+            if (sec0 < out1 && out0 < sec1)
+                return fail(SDA_ERR_INVALID_ARGUMENT, "d_masked overlaps d_secrets: the ChaCha kind does not mask in place");
+        }
+        SDA_TRY(c.ctx.use());
+        hipStream_t s = c.ctx.pick(stream);
+        const size_t nw = c.seed_words();
+        WipedVec<uint32_t> raw(participants * nw ? participants * nw : 1);
+        if (seed_words) memcpy(raw.data(), seed_words, participants * nw * 4);
+        else SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
+        WipedVec<int64_t> words(participants * nw ? participants * nw : 1);
+        WipedVec<uint32_t> key8(participants * 8, 0u);
+        for (size_t p = 0; p < participants; ++p)
+            for (size_t i = 0; i < nw; ++i) {
+                words[p * nw + i] = (int64_t)raw[p * nw + i];
+                if (i < 8) key8[p * 8 + i] = raw[p * nw + i];
+            }
+        SDA_TRY(mask_chunk_scratch(c, participants, s));
+        const size_t words_bytes = participants * nw * 8;
+        SDA_TRY(c.d_words.reserve_wiped(words_bytes));
+        const MaskApply apply{d_secrets, secrets_stride, d_masked, masked_stride, c.mod};
+        SDA_TRY(end_synchronised(s, [&]() -> int {                            // the host vectors above are in flight until it returns
+            const int st = [&]() -> int {
+                if (words_bytes) HIP_TRY(hipMemcpyAsync(c.d_words.p, words.data(), words_bytes, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8.data(), participants * 32, hipMemcpyHostToDevice, s));
+                SDA_TRY(chacha_expand(c, participants, false, len, &apply, s));
+                return capi_sealedbox_seal_share_rows(b, pk, 1, participants, esk, VarintRows{c.d_words.as<int64_t>(), participants, nw, nw},
+                                                      d_boxes, slot_bytes, d_row_bytes, s);
+            }();
+            // whatever became of the call: the seed rows and their keys do not outlive it
+            const hipError_t z0 = hipMemsetAsync(c.d_words.p, 0, c.d_words.cap, s), z1 = hipMemsetAsync(c.d_seeds.p, 0, participants * 32, s);
+            SDA_TRY(st);
+            HIP_TRY(z0);
+            HIP_TRY(z1);
+            return SDA_OK;
+        }));
+        note_kernel("chacha_expand (apply) + varint_seal_stream_kernel + sbox_poly_kernel");
+        snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+        return SDA_OK;
+    }
+    // Full - full.rs:21-35
+    SDA_TRY(check_streams(first_participant, participants));
+    if (participants == 0) return SDA_OK;
+    SDA_TRY(c.ctx.use());
+    MaskJob J{};
+    J.secrets = d_secrets; J.secrets_stride = secrets_stride; J.masked = d_masked; J.masked_stride = masked_stride;
+    J.len = len; J.participants = participants; J.first_participant = first_participant; J.mod = c.mod;
+    // like mask_batch_dev: nothing is drawn for empty rows, every other call runs under its own call key
+    if (len > 0) J.key = c.drbg.call_key();
+    const int st = capi_sealedbox_seal_masked_rows(b, pk, esk, J, c.drbg.rounds, d_boxes, slot_bytes, d_row_bytes, c.ctx.pick(stream));
+    explicit_bzero(&J.key, sizeof J.key);
+    if (st != SDA_OK) return st;
+    note_kernel("mask_seal_stream_kernel<%d> + sbox_poly_kernel", c.drbg.rounds);      // the whole call, not only its last launch
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_masker_mask_sealed_rows_dev(sda_secret_masker_t* m, sda_varint_codec_t* codec, sda_sealedbox_t* b,
+                                                      const uint8_t pk[32], const uint8_t* esk, const int64_t* d_secrets,
+                                                      size_t participants, size_t len, size_t secrets_stride,
+                                                      uint64_t first_participant, int64_t* d_masked, size_t masked_stride,
+                                                      uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, void* stream) {
+    return mask_sealed_rows_dev(m, nullptr, codec, b, pk, esk, d_secrets, participants, len, secrets_stride, first_participant, d_masked,
+                                masked_stride, d_boxes, slot_bytes, d_row_bytes, stream);
+}
+#ifdef SDA_TEST_HOOKS
+// the ChaCha kind of the call above with chosen seeds (as sda_debug_secret_masker_mask_batch_seeded_dev)
+extern "C" int sda_debug_secret_masker_mask_sealed_rows_seeded_dev(sda_secret_masker_t* m, const unsigned* seed_words,
+                                                                   sda_varint_codec_t* codec, sda_sealedbox_t* b, const uint8_t pk[32],
+                                                                   const uint8_t* esk, const int64_t* d_secrets, size_t participants,
+                                                                   size_t len, size_t secrets_stride, uint64_t first_participant,
+                                                                   int64_t* d_masked, size_t masked_stride, uint8_t* d_boxes,
+                                                                   size_t slot_bytes, uint64_t* d_row_bytes, void* stream) {
+    if (!m || !seed_words) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m->core.scheme.kind != SDA_MASKING_CHACHA) return fail(SDA_ERR_INVALID_ARGUMENT, "only the ChaCha kind takes seeds");
+    return mask_sealed_rows_dev(m, seed_words, codec, b, pk, esk, d_secrets, participants, len, secrets_stride, first_participant,
+                                d_masked, masked_stride, d_boxes, slot_bytes, d_row_bytes, stream);
+}
+#endif
 
 // the clerk's last step (clerk.rs:84-100): the sums reduced, encoded and sealed to the recipient, every row split over the chip -
 // setup, block lengths, scan, ONE pass that reduces, encodes and encrypts, tags.  No plaintext result, no wire buffer.

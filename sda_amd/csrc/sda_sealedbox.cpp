@@ -195,6 +195,26 @@ int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, con
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing generated share rows: launch failed: %s", hipGetErrorString(e));
 }
 
+// for sda_secret_masker_mask_sealed_rows_dev (sda_capi.cpp, the Full kind), which has checked the arguments: as above, the encode
+// pass drawing the masks it encodes and storing the masked secrets; one key, rows = participants
+int capi_sealedbox_seal_masked_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const MaskJob& J, int rounds,
+                                    uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
+    const size_t rows = J.participants, max_msg = J.len * 10;
+    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
+    if (int st = scratch(b, rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
+    uint8_t *d_esk = nullptr, *d_pks = nullptr;
+    if (int st = stage_keys(b, pk, 1, esk, rows, s, &d_esk, &d_pks)) return st;
+    SboxState* d_states = static_cast<SboxState*>(b->d_states);
+    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
+    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, 1, rows, d_boxes, slot_bytes, rows, d_states, s);
+    if (e == hipSuccess) e = launch_mask_seal_stream(J, rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    if (e == hipSuccess)
+        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing masked rows: launch failed: %s", hipGetErrorString(e));
+}
+
 // for sda_share_combiner_finish_sealed_rows_dev (sda_capi.cpp), which has checked the arguments and reserved the scan scratch
 // (d_block_bytes / d_block_off: jobs * sum_seal_blocks(len) entries; d_scan_aux: scan_aux_entries of that; d_scan_total: 8 bytes):
 // as above with the rows computed from the clerk sums and every row split over the chip - lengths, scan, encode + encrypt

@@ -1219,6 +1219,80 @@ __global__ __launch_bounds__(kStreamWaves * 64) void share_seal_stream_kernel(Sh
     encode_row(vals, J.batches, r, boxes + r * slot + 48, tiles[wave], msg_bytes, crypt);
 }
 
+// ---- secrets -> masked secrets and the sealed mask rows without the masks (participate.rs:52-72: mask the secrets, seal the mask to
+// the recipient; full.rs:21-35) ---
+// The seal kernel again, the row's values DRAWN: row p is participant p's mask, the sda-drbg-v1 draws of stream first_participant + p
+// with T = 1 - what full_mask_drbg_kernel draws.  Lane l of step j owns elements 128 j + 2 l and + 1 = pair 64 j + l of the DPP-quad
+// CSPRNG, so drbg_pair() hands the lane its two masks; all 64 lanes draw in every step (a quad must be whole), the lanes past the
+// row's end store nothing and encode_row gives their values the length 0.  The same lane adds the masks onto its two secrets and
+// stores the masked secrets; the masks go on to the encode loop and exist in registers only.  Each element is read once and
+// written once by the lane that read it, so masked == secrets (equal strides) is fine.
+template <int ROUNDS>
+struct MaskValues {
+    static constexpr int kDepth = 1;          // nothing is prefetched: the step loop stays rolled
+    const MaskJob& J;
+    const int64_t* sp;                        // the participant's secrets ...
+    int64_t* mp;                              // ... and masked secrets (may be the same row)
+    uint64_t stream;
+    bool vec;                                 // wave-uniform: both rows 16-byte aligned
+    QuadCol qc;
+    __device__ __forceinline__ MaskValues(const MaskJob& J_, uint64_t p) : J(J_) {
+        sp = J.secrets + p * J.secrets_stride;
+        mp = J.masked + p * J.masked_stride;
+        stream = J.first_participant + p;
+        vec = ((((uintptr_t)sp) | ((uintptr_t)mp)) & 15u) == 0;
+        qc = quad_col(J.key);
+    }
+    __device__ __forceinline__ void get(int, uint64_t j, int64_t& x, int64_t& y) {
+        typedef long long ll2v __attribute__((ext_vector_type(2)));
+        const uint64_t pair = j * (kEncVals / 2) + (threadIdx.x & 63u);
+        const uint64_t b0 = 2 * pair;
+        const bool two = vec && b0 + 1 < J.len;                       // the odd tail and a misaligned row take 8-byte accesses
+        const bool one0 = !two && b0 < J.len, one1 = !two && b0 + 1 < J.len;
+        // the secrets first: the ChaCha rounds of the draw cover the load's latency
+        long long s0 = 0, s1 = 0;
+        if (two) {
+            const ll2v v = __builtin_nontemporal_load(reinterpret_cast<const ll2v*>(sp + b0));
+            s0 = v.x; s1 = v.y;
+        }
+        if (one0) s0 = __builtin_nontemporal_load(reinterpret_cast<const long long*>(sp + b0));
+        if (one1) s1 = __builtin_nontemporal_load(reinterpret_cast<const long long*>(sp + b0 + 1));
+        __builtin_amdgcn_sched_barrier(0);
+        uint64_t r0, r1;
+        drbg_pair<ROUNDS>(J.key, qc, stream, pair, 1, 0, J.mod, r0, r1);
+        const uint64_t m = J.mod.m, mu = J.mod.mu;
+        const long long m0 = (long long)addmod(canon_i64(s0, m, mu), r0, m);
+        const long long m1 = (long long)addmod(canon_i64(s1, m, mu), r1, m);
+        if (two) {
+            ll2v v;
+            v.x = m0; v.y = m1;
+            __builtin_nontemporal_store(v, reinterpret_cast<ll2v*>(mp + b0));
+        }
+        if (one0) __builtin_nontemporal_store(m0, reinterpret_cast<long long*>(mp + b0));
+        if (one1) __builtin_nontemporal_store(m1, reinterpret_cast<long long*>(mp + b0 + 1));
+        x = (int64_t)r0; y = (int64_t)r1;
+    }
+};
+
+// One wave per participant row, kStreamWaves rows per workgroup
+template <int ROUNDS>
+__global__ __launch_bounds__(kStreamWaves * 64) void mask_seal_stream_kernel(MaskJob J, uint8_t* __restrict__ boxes, uint64_t slot,
+                                                                             const SboxState* __restrict__ states,
+                                                                             uint64_t* __restrict__ msg_bytes) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[kStreamWaves][kEncTile];
+    __shared__ uint32_t kstream[kStreamWaves][kKsTile];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t p = (uint64_t)blockIdx.x * kStreamWaves + wave;
+    if (p >= J.participants) return;
+    // a recipient key that gave the all-zero shared secret: the row is refused (varint_seal_stream_kernel) and, nothing being
+    // drawn, its secrets stay unmasked - masked row p is left as it was
+    if (states[p].bad) { if ((threadIdx.x & 63) == 0) msg_bytes[p] = 0; return; }
+    EncXSalsa crypt;
+    crypt.open(states[p], kstream[wave]);
+    MaskValues<ROUNDS> vals(J, p);
+    encode_row(vals, J.len, p, boxes + p * slot + 48, tiles[wave], msg_bytes, crypt);
+}
+
 // ---- clerk sums -> the sealed clerking result, every row split over the chip (clerk.rs:84-100: reduce, encode_var, seal) ---------
 // A clerk has ONE result row per job, so the one-wave-per-row seal above would put a whole job on one wave.  Here a row is cut
 // into blocks of kSumVals values, one workgroup each, in the three passes of the scan-form encoder - lengths, scan, write - with
@@ -1444,6 +1518,21 @@ hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_bo
         case 20: share_seal_stream_kernel<20><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
         case 12: share_seal_stream_kernel<12><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
         case 8: share_seal_stream_kernel<8><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_seal_stream(const MaskJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
+                                   uint64_t* d_msg_bytes, hipStream_t s) {
+    if (J.participants == 0) return hipSuccess;
+    const uint64_t groups = vceil(J.participants, kStreamWaves);
+    if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)groups), block(kStreamWaves * 64);
+    switch (rounds) {
+        case 20: mask_seal_stream_kernel<20><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        case 12: mask_seal_stream_kernel<12><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
+        case 8: mask_seal_stream_kernel<8><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

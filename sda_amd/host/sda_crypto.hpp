@@ -405,6 +405,38 @@ struct SecretMasker {
         return {m, ms};
     }
 };
+/// new_participation's masking and recipient encryption (participate.rs:52-72) for ONE participant through ONE call
+/// (sda_secret_masker_mask_sealed_rows_dev): the secrets go in, the masked secrets and the mask's encryption for the recipient
+/// come out.  Full: the mask is never written to device memory; ChaCha: the sealed mask is the seed.  The None scheme has no
+/// recipient encryption (SDA_ERR_UNSUPPORTED).  esk: null, or 32 bytes of an injected ephemeral secret (tests only).
+inline std::pair<Encryption, std::vector<MaskedSecret>> mask_sealed(SecretMasker& masker, ShareCodec& codec, SealedBox& box,
+                                                                    const EncryptionKey& recipient_key,
+                                                                    const std::vector<Secret>& secrets, const uint8_t* esk = nullptr) {
+    if (recipient_key.size() != 32) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "mask_sealed: the recipient key is 32 bytes");
+    const size_t len = secrets.size(), slot = sda_varint_slot_size(sda_secret_masker_mask_len(masker.h, len)) + SDA_SEALBYTES;
+    struct Dev {                                                    // freed on every way out
+        void* p = nullptr;
+        ~Dev() { if (p) sda_dev_free(p); }
+    } d_secrets, d_masked, d_box, d_len;
+    detail::check(sda_dev_malloc(&d_secrets.p, len * sizeof(Secret) + 16));
+    detail::check(sda_dev_malloc(&d_masked.p, len * sizeof(MaskedSecret) + 16));
+    detail::check(sda_dev_malloc(&d_box.p, slot));
+    detail::check(sda_dev_malloc(&d_len.p, sizeof(uint64_t)));
+    if (len) detail::check(sda_dev_upload(d_secrets.p, secrets.data(), len * sizeof(Secret)));
+    detail::check(sda_secret_masker_mask_sealed_rows_dev(masker.h, codec.h, box.h, recipient_key.data(), esk,
+                                                         static_cast<const int64_t*>(d_secrets.p), 1, len, len, 0,
+                                                         static_cast<int64_t*>(d_masked.p), len, static_cast<uint8_t*>(d_box.p), slot,
+                                                         static_cast<uint64_t*>(d_len.p), nullptr));
+    detail::check(sda_dev_synchronize());
+    uint64_t n = 0;
+    detail::check(sda_dev_download(&n, d_len.p, sizeof n));
+    if (n == 0) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "sealing refused: the recipient public key is a small-order point");
+    Encryption e(n);
+    detail::check(sda_dev_download(e.data(), d_box.p, n));
+    std::vector<MaskedSecret> ms(len);
+    if (len) detail::check(sda_dev_download(ms.data(), d_masked.p, len * sizeof(MaskedSecret)));
+    return {e, ms};
+}
 
 struct MaskCombiner {
     sda_mask_combiner_t* h = nullptr;
