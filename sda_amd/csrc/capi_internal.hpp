@@ -7,30 +7,32 @@
 int capi_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets sda_last_error(), returns code
 int capi_make_mod(int64_t modulus, sda::ModParams& mod);                                  // validated Barrett / Lemire constants
 int capi_device_ready();                                                                  // a device exists; make the selected one current
+struct sda_sealedbox;
+// rows that are still sealed boxes, as every update_sealed_rows_dev entry point takes them (the SDAJOBv1 SEALED layout)
+struct SealedRows {
+    const uint8_t* d_boxes; size_t slot_bytes; const uint64_t* d_row_bytes; size_t rows, max_box_bytes;
+    uint32_t *d_ok, *d_status;
+};
 // first half of a sealed-box open on the handle's scratch (sda_sealedbox.cpp): every tag verified, d_ok / *d_status |= 16 /
 // SboxState.bad written as sda_sealedbox_open_rows_dev writes them, NO keystream pass.  *d_states: the per-row states.
-struct sda_sealedbox;
-int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot_bytes,
-                               const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status,
-                               int device, hipStream_t s, const sda::SboxState** d_states);
-// sda_sealedbox_seal_share_rows_dev after its argument checks (sda_sealedbox.cpp): stage the keys, setup, encode + encrypt in one
-// pass (launch_varint_seal_stream), authenticate, wipe the ephemeral secrets - all on the handle's scratch
-int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key, const uint8_t* esk,
-                                   const sda::VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
-// sda_share_generator_generate_sealed_rows_dev after its argument checks: the same sequence with the rows computed from the
-// secrets inside the encode pass (launch_share_seal_stream); n keys, rows_per_key = participants
-int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, const uint8_t* esk, const sda::ShareJob& J, int rounds,
-                                       uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
-// sda_secret_masker_mask_sealed_rows_dev (Full) after its argument checks: the same sequence with the rows drawn inside the encode
-// pass, which also stores the masked secrets (launch_mask_seal_stream); one key, rows = J.participants
-int capi_sealedbox_seal_masked_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const sda::MaskJob& J, int rounds,
-                                    uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
-// sda_share_combiner_finish_sealed_rows_dev after its argument checks: the same sequence with the rows computed from the clerk
-// sums S and every row split over the chip (launch_sum_lengths, launch_scan_u32, launch_sum_seal_wide); one key, rows = S.jobs.
-// The scan scratch is the caller's (the codec handle's): d_block_bytes and d_block_off hold S.jobs * sum_seal_blocks(S.len) entries
-int capi_sealedbox_seal_summed_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const sda::SumRows& S,
-                                    uint32_t* d_block_bytes, uint64_t* d_block_off, uint64_t* d_scan_total, uint64_t* d_scan_aux,
-                                    uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s);
+int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const SealedRows& R, int device, hipStream_t s,
+                               const sda::SboxState** d_states);
+// the keys of a seal: row r goes to pks[r / rows_per_key]; esk: a secret per row, NULL draws them from the OS
+struct SealKeys { const uint8_t* pks; size_t n_pks, rows_per_key; const uint8_t* esk; };
+// the encode pass of a seal, by reference (two words, no allocation): a callable (const SboxState* d_states, uint64_t* d_msg_bytes,
+// hipStream_t) -> hipError_t that must outlive the call it is passed to - a lambda written in the argument list does
+class EncodePass {
+    const void* f_;
+    hipError_t (*call_)(const void*, const sda::SboxState*, uint64_t*, hipStream_t);
+public:
+    template <typename F>
+    EncodePass(const F& f) : f_(&f), call_([](const void* p, const sda::SboxState* st, uint64_t* lens, hipStream_t s) { return (*static_cast<const F*>(p))(st, lens, s); }) {}
+    hipError_t operator()(const sda::SboxState* st, uint64_t* lens, hipStream_t s) const { return call_(f_, st, lens, s); }
+};
+// every sealed-row producer after its argument checks (sda_sealedbox.cpp), all on the handle's scratch: stage the keys, setup, the
+// caller's encode + encrypt pass, authenticate, wipe the ephemeral secrets.  max_msg: a row's longest plaintext; what: for the error text
+int capi_sealedbox_seal(sda_sealedbox* b, const SealKeys& K, size_t rows, size_t max_msg, uint8_t* d_boxes, size_t slot_bytes,
+                        uint64_t* d_row_bytes, hipStream_t s, const char* what, EncodePass encode);
 int capi_sealedbox_device(const sda_sealedbox* b);
 
 // ---- path-selection knobs (A/B measurements and parity tests of the non-default kernels) -----------------------------------

@@ -174,6 +174,11 @@ void sda::note_kernel(const char* fmt, ...) {
     vsnprintf(g_last_gen_kernel, sizeof g_last_gen_kernel, fmt, ap);
     va_end(ap);
 }
+// what sda_debug_last_kernel reports is a whole call, not only its last launch: the noted kernel(s), then sep + tail
+static void publish_kernels(const char* sep = "", const char* tail = "") {
+    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s%s%s", g_last_gen_kernel, sep, tail);
+}
+#define NOTE_CALL_KERNELS(...) (note_kernel(__VA_ARGS__), publish_kernels())    // for a call that names its launches itself
 extern "C" const char* sda_debug_last_kernel(void) { return g_last_call_kernels; }
 static thread_local char g_last_reveal_kernel[96];     // the last one-shot reveal kernel instance launched on this thread
 void sda::note_reveal_kernel(const char* fmt, ...) {
@@ -409,6 +414,46 @@ int check_streams(uint64_t first, uint64_t count) {
         return fail(SDA_ERR_INVALID_ARGUMENT, "CSPRNG stream ids must stay below 2^56 (first_participant %llu + %llu participants)",
                     (unsigned long long)first, (unsigned long long)count);
     return SDA_OK;
+}
+
+// ---- what the slotted and the sealed *_dev calls check alike ----
+// slotted rows: row r at d_bytes + r * slot_bytes, every row on the 16-byte grid.  noun: "slots" of varint rows, "boxes"
+int check_slots(const char* noun, const void* d_bytes, size_t slot_bytes) {
+    if (slot_bytes % 16 || ((uintptr_t)d_bytes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "%s must be 16-byte aligned (buffer and slot_bytes)", noun);
+    return SDA_OK;
+}
+// a box slot holds the varints of `values` values plus the 48 seal bytes; what: `values` as the caller knows it
+int check_seal_room(size_t slot_bytes, size_t values, const char* what) {
+    if (values > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(values) + SDA_SEALBYTES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(%s) + 48", what);
+    return SDA_OK;
+}
+// the handles of a sealed call live on one device: the sealed-box handle and the codec, and `who` (nullptr: no third handle)
+int check_one_device(const sda_sealedbox* b, int codec_device, const char* who = nullptr, int who_device = -1) {
+    const int box_device = capi_sealedbox_device(b);
+    if (box_device == codec_device && (!who || who_device == codec_device)) return SDA_OK;
+    if (!who) return fail(SDA_ERR_INVALID_ARGUMENT, "the sealed-box handle lives on device %d, the codec on device %d", box_device, codec_device);
+    return fail(SDA_ERR_INVALID_ARGUMENT, "the %s lives on device %d, the sealed-box handle on device %d, the codec on device %d", who, who_device,
+                box_device, codec_device);
+}
+// what every wire-fed update (varint bytes or sealed boxes into running sums) checks first, in this order; keys: the sealed forms' pk && sk
+int check_wire_fed(bool handles, bool keys, bool begun, bool rust_signed) {
+    if (!handles) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!keys) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!begun) return fail(SDA_ERR_STATE, "update before begin");
+    if (rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    return SDA_OK;
+}
+// a sealed update after its state checks and its empty-work return: the rows' pointers and slots, then the handle's device, the
+// stream (*s) and the tag pass on it - what the entry point launches next reads *d_states
+int sealed_rows_verify(const Ctx& ctx, sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const SealedRows& R, void* stream,
+                       hipStream_t* s, const SboxState** d_states) {
+    if (!R.d_status || !R.d_boxes || !R.d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
+    SDA_TRY(check_slots("boxes", R.d_boxes, R.slot_bytes));
+    if (R.max_box_bytes > R.slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
+    SDA_TRY(ctx.use());
+    *s = ctx.pick(stream);
+    return capi_sealedbox_verify_rows(b, pk, sk, R, ctx.device, *s, d_states);
 }
 
 bool sharing_is_additive(const sda_sharing_scheme_t* s) { return s->kind == SDA_SHARING_ADDITIVE; }
@@ -1327,7 +1372,7 @@ extern "C" int sda_share_generator_generate_batch_dev(sda_share_generator_t* g, 
     g_last_gen_kernel[0] = 0;
     const int st = generate_batch_impl(g, key, d_secrets, participants, len, secrets_stride, d_rand, rand_stride, first_participant,
                                        d_out, out_stride_participant, out_stride_clerk, stream);
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    publish_kernels();
     explicit_bzero(&key, sizeof key);
     return st;
 }
@@ -1358,7 +1403,7 @@ extern "C" int sda_share_generator_generate(sda_share_generator_t* g, const int6
     g_last_gen_kernel[0] = 0;
     int st = generate_batch_impl(g, key, g->d_secrets.as<int64_t>(), 1, len, len, d_rand, want_rand, stream_id,
                                  g->d_out.as<int64_t>(), (size_t)g->n * Bs, Bs, nullptr);
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    publish_kernels();
     explicit_bzero(&key, sizeof key);
     if (st == SDA_OK) {
         hipError_t e = hipMemcpy2DAsync(out, B * 8, g->d_out.p, Bs * 8, B * 8, g->n, hipMemcpyDeviceToHost, g->ctx.stream);
@@ -1594,9 +1639,9 @@ extern "C" int sda_share_generator_generate_combine_dev(sda_share_generator_t* g
         const int mp = c->mark_pending(s);
         if (st == SDA_OK) st = mp;
     }
-    if (fused) snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
-    else snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s%s%s", g_last_gen_kernel, g_last_gen_kernel[0] && prev_participants ? " + " : "",
-                  prev_participants ? (side ? "combine_update_walk_kernel (side stream)" : "combine_update_kernel (two launches)") : "");
+    if (fused) publish_kernels();
+    else publish_kernels(g_last_gen_kernel[0] && prev_participants ? " + " : "",
+                         prev_participants ? (side ? "combine_update_walk_kernel (side stream)" : "combine_update_kernel (two launches)") : "");
     return st;
 }
 
@@ -1921,31 +1966,23 @@ extern "C" int sda_secret_reconstructor_update_sealed_rows_dev(sda_secret_recons
                                                                size_t first_pos, const uint8_t* d_boxes, size_t slot_bytes,
                                                                const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes,
                                                                uint32_t* d_ok, uint32_t* d_status, void* stream) {
-    if (!r || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!r->job_begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (r->job_acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update_dev");
+    SDA_TRY(check_wire_fed(r && codec && b, pk && sk, r && r->job_begun, r && r->job_acc.rust_signed));
     if (rows == 0) return SDA_OK;
     SDA_TRY(job_claim(r, first_pos, rows, false));
-    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
-    SDA_TRY(r->ctx.use());
-    hipStream_t s = r->ctx.pick(stream);
+    hipStream_t s = nullptr;
     const SboxState* d_states = nullptr;
-    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, r->ctx.device, s,
-                                       &d_states));
+    SDA_TRY(sealed_rows_verify(r->ctx, b, pk, sk, SealedRows{d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status}, stream, &s,
+                               &d_states));
     if (r->additive) {
         int waves = 0;
         HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, r->job_row_len,
                                              r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), d_status, s, &waves));
-        note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
+        NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
     } else {
         HIP_TRY(launch_sealed_stream_weighted(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, r->job_row_len, first_pos,
                                               r->job(), r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), d_status, s));
-        note_kernel("sbox_poly_kernel + sealed_stream_weighted_kernel<8, %s>", r->k <= 16 ? "lds" : "global");
+        NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_weighted_kernel<8, %s>", r->k <= 16 ? "lds" : "global");
     }
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);     // the whole call, not only its last launch
     return job_claim(r, first_pos, rows, true);
 }
 
@@ -2100,6 +2137,45 @@ int end_synchronised(hipStream_t s, Enqueue&& enqueue) {
     HIP_TRY(se);
     return SDA_OK;
 }
+
+// ---- what the ChaCha kind checks and draws before it masks (chacha.rs:24-33), host form and device tiles alike ----
+int check_chacha_dimension(const MaskCore& c, size_t len) {
+    if (len != c.scheme.dimension)
+        return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (dimension %llu, secrets %zu) - chacha.rs:26",
+                    (unsigned long long)c.scheme.dimension, len);
+    return SDA_OK;
+}
+// a repair writes a position a second time from secrets[p][i]: in place it would add a second mask to the first.  Refused for every
+// (modulus, dimension), also where no repair can happen, so that the rule does not depend on the plan
+int check_not_in_place(const int64_t* d_secrets, size_t secrets_stride, const int64_t* d_masked, size_t masked_stride, size_t participants,
+                       size_t len) {
+    if (participants == 0 || len == 0) return SDA_OK;
+    const uintptr_t sec0 = reinterpret_cast<uintptr_t>(d_secrets), out0 = reinterpret_cast<uintptr_t>(d_masked);
+    const uintptr_t sec1 = sec0 + ((participants - 1) * secrets_stride + len) * 8, out1 = out0 + ((participants - 1) * masked_stride + len) * 8;
+    if (sec0 < out1 && out0 < sec1) return fail(SDA_ERR_INVALID_ARGUMENT, "d_masked overlaps d_secrets: the ChaCha kind does not mask in place");
+    return SDA_OK;
+}
+// one seed per participant, from the OS (chacha.rs:29-33) or the test hook's seed_words (host [participants][nw]): raw as drawn,
+// words as the participant sends them (its "mask" is its seed, chacha.rs:48-50), key8 as the kernels take them.  All three are
+// wiped when they die, and a caller that copies from them asynchronously keeps them alive until its stream is synchronised
+struct ChaChaSeeds {
+    const size_t participants, nw;
+    WipedVec<uint32_t> raw;
+    WipedVec<int64_t> words;
+    WipedVec<uint32_t> key8;
+    ChaChaSeeds(size_t participants, size_t nw)
+        : participants(participants), nw(nw), raw(participants * nw ? participants * nw : 1), words(raw.size()), key8(participants * 8, 0u) {}
+    int draw(const uint32_t* seed_words) {
+        if (seed_words) memcpy(raw.data(), seed_words, participants * nw * 4);
+        else SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
+        for (size_t p = 0; p < participants; ++p)
+            for (size_t i = 0; i < nw; ++i) {
+                words[p * nw + i] = (int64_t)raw[p * nw + i];
+                if (i < 8) key8[p * 8 + i] = raw[p * nw + i];
+            }
+        return SDA_OK;
+    }
+};
 }  // namespace
 
 #ifdef SDA_TEST_HOOKS
@@ -2184,9 +2260,7 @@ extern "C" int sda_secret_masker_mask(sda_secret_masker_t* m, const int64_t* sec
         return SDA_OK;
     }
     const size_t want_mask = (size_t)sda_secret_masker_mask_len(m, len);
-    if (c.scheme.kind == SDA_MASKING_CHACHA && len != c.scheme.dimension)
-        return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (dimension %llu, secrets %zu) - chacha.rs:26",
-                    (unsigned long long)c.scheme.dimension, len);
+    if (c.scheme.kind == SDA_MASKING_CHACHA) SDA_TRY(check_chacha_dimension(c, len));
     if (want_mask > 0 && (!mask_out || mask_cap < want_mask)) return fail(SDA_ERR_INVALID_ARGUMENT, "mask buffer too small (need %zu)", want_mask);
     if (rand && rand_len != want_mask) return fail(SDA_ERR_INVALID_ARGUMENT, "rand_len must be %zu (got %zu)", want_mask, rand_len);
     SDA_TRY(c.ctx.use());
@@ -2269,35 +2343,19 @@ static int mask_batch_dev(sda_secret_masker_t* m, const uint32_t* seed_words, co
     if (!d_secrets || !d_masked) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (secrets_stride < len || masked_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "stride < len");
     if (c.scheme.kind == SDA_MASKING_CHACHA) {                                // chacha.rs:24-54 for every participant
-        if (len != c.scheme.dimension)
-            return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (dimension %llu, secrets %zu) - chacha.rs:26",
-                        (unsigned long long)c.scheme.dimension, len);
+        SDA_TRY(check_chacha_dimension(c, len));
         const size_t nw = c.seed_words();
         if (!d_masks || mask_stride < nw) return fail(SDA_ERR_INVALID_ARGUMENT, "d_masks must hold %zu seed words per participant", nw);
-        // a repair writes a position a second time from secrets[p][i]: in place it would add a second mask to the first.  Refused
-        // for every (modulus, dimension), also where no repair can happen, so that the rule does not depend on the plan
-        const uintptr_t sec0 = reinterpret_cast<uintptr_t>(d_secrets), out0 = reinterpret_cast<uintptr_t>(d_masked);
-        const uintptr_t sec1 = sec0 + ((participants - 1) * secrets_stride + len) * 8, out1 = out0 + ((participants - 1) * masked_stride + len) * 8;
-        if (sec0 < out1 && out0 < sec1)
-            return fail(SDA_ERR_INVALID_ARGUMENT, "d_masked overlaps d_secrets: the ChaCha kind does not mask in place");
+        SDA_TRY(check_not_in_place(d_secrets, secrets_stride, d_masked, masked_stride, participants, len));
         SDA_TRY(c.ctx.use());
         hipStream_t s = c.ctx.pick(stream);
-        // one OS-entropy seed per participant (chacha.rs:29-33); the "mask" a participant sends is its seed (chacha.rs:48-50)
-        WipedVec<uint32_t> raw(participants * nw ? participants * nw : 1);
-        if (seed_words) memcpy(raw.data(), seed_words, participants * nw * 4);
-        else SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
-        WipedVec<int64_t> words(participants * nw);
-        WipedVec<uint32_t> key8(participants * 8, 0u);
-        for (size_t p = 0; p < participants; ++p)
-            for (size_t i = 0; i < nw; ++i) {
-                words[p * nw + i] = (int64_t)raw[p * nw + i];
-                if (i < 8) key8[p * 8 + i] = raw[p * nw + i];
-            }
+        ChaChaSeeds seeds(participants, nw);
+        SDA_TRY(seeds.draw(seed_words));
         SDA_TRY(mask_chunk_scratch(c, participants, s));
         const MaskApply apply{d_secrets, secrets_stride, d_masked, masked_stride, c.mod};
-        return end_synchronised(s, [&]() -> int {                             // the host vectors above are in flight until it returns
-            HIP_TRY(hipMemcpy2DAsync(d_masks, mask_stride * 8, words.data(), nw * 8, nw * 8, participants, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8.data(), participants * 32, hipMemcpyHostToDevice, s));
+        return end_synchronised(s, [&]() -> int {                             // `seeds` is in flight until it returns
+            HIP_TRY(hipMemcpy2DAsync(d_masks, mask_stride * 8, seeds.words.data(), nw * 8, nw * 8, participants, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(c.d_seeds.p, seeds.key8.data(), participants * 32, hipMemcpyHostToDevice, s));
             return chacha_expand(c, participants, false, len, &apply, s);
         });
     }
@@ -2438,8 +2496,7 @@ extern "C" int sda_mask_combiner_update_dev(sda_mask_combiner_t* mc, const int64
         HIP_TRY(launch_mask_rows_to_keys(d_rows + r0 * row_stride, ns, row_len, row_stride, c.d_seeds.as<uint32_t>(), s));
         SDA_TRY(chacha_expand(c, ns, false, c.job_dimension, nullptr, s));
     }
-    note_kernel("mask_rows_to_keys_kernel + chacha_mask_fast_kernel + %s", kMaskRepairKernels);          // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    NOTE_CALL_KERNELS("mask_rows_to_keys_kernel + chacha_mask_fast_kernel + %s", kMaskRepairKernels);
     return SDA_OK;
 }
 
@@ -2451,25 +2508,17 @@ extern "C" int sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* mc,
     MaskCore& c = mc->core;
     if (c.scheme.kind == SDA_MASKING_NONE)                                    // a None mask is empty: there is no box to open
         return c.begun ? fail(SDA_ERR_UNSUPPORTED, "the None scheme has no masks to unseal (none.rs:21-26)") : fail(SDA_ERR_STATE, "update before begin");
-    if (!codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c.begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (c.acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update_dev");
+    SDA_TRY(check_wire_fed(codec && b, pk && sk, c.begun, c.acc.rust_signed));
     if (rows == 0) return SDA_OK;
-    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
-    SDA_TRY(c.ctx.use());
-    hipStream_t s = c.ctx.pick(stream);
+    hipStream_t s = nullptr;
     const SboxState* d_states = nullptr;
-    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, c.ctx.device, s,
-                                       &d_states));
+    SDA_TRY(sealed_rows_verify(c.ctx, b, pk, sk, SealedRows{d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status}, stream, &s,
+                               &d_states));
     if (c.scheme.kind == SDA_MASKING_FULL) {                                  // a row is a mask vector: the clerk's sealed sum
         int waves = 0;
         HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, c.job_dimension,
                                              c.acc.lo.as<uint64_t>(), c.acc.hi.as<int64_t>(), d_status, s, &waves));
-        note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
-        snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+        NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
         return SDA_OK;
     }
     // ChaCha: a row is the varint encoding of a seed (sodium.rs:36-43).  With dimension 0 the rows are still verified and decoded
@@ -2481,8 +2530,7 @@ extern "C" int sda_mask_combiner_update_sealed_rows_dev(sda_mask_combiner_t* mc,
                                         c.d_seeds.as<uint32_t>(), plan + PLAN_KEYS, d_status, s));
         SDA_TRY(chacha_expand(c, ns, true, c.job_dimension, nullptr, s));
     }
-    note_kernel("sbox_poly_kernel + sealed_seed_keys_kernel + chacha_mask_fast_counted_kernel + %s", kMaskRepairKernels);
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_seed_keys_kernel + chacha_mask_fast_counted_kernel + %s", kMaskRepairKernels);
     return SDA_OK;
 }
 
@@ -2717,13 +2765,23 @@ extern "C" int sda_varint_decode(sda_varint_codec_t* c, const uint8_t* bytes, si
     return SDA_OK;
 }
 
+// job-major rows straight from their wire bytes into the sums: 16 rows of a job per workgroup, decoded values summed in an LDS
+// column window - no decoded tile.  With dimension 0 that launch reads nothing, so a decode pass sets the rows' status
+static int stream_combine(sda_share_combiner* c, const uint8_t* d_bytes, size_t n_bytes, const RowRanges& rr, size_t rows, uint32_t* d_status,
+                          hipStream_t s) {
+    const size_t L = c->dimension;
+    SDA_TRY(c->join_pending(s));
+    HIP_TRY(launch_varint_stream_combine(d_bytes, n_bytes, rr, c->jobs, rows / c->jobs, L, c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(),
+                                         d_status, s));
+    if (L == 0) HIP_TRY(launch_varint_stream_decode(d_bytes, n_bytes, rr, rows, 0, 0, nullptr, d_status, s));
+    return c->mark_pending(s);
+}
+
 // streaming clerk: wire-format vectors -> decode tile -> clerk-sum update -> discard (clerk.rs:71-86)
 extern "C" int sda_share_combiner_update_varint_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec,
                                                     const uint8_t* d_bytes, size_t n_bytes, const uint64_t* d_row_offsets,
                                                     size_t rows, uint32_t* d_status, void* stream) {
-    if (!c || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!c->begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    SDA_TRY(check_wire_fed(c && codec, true, c && c->begun, c && c->acc.rust_signed));
     if (rows == 0 || c->jobs == 0) return SDA_OK;
     if (rows % c->jobs) return fail(SDA_ERR_INVALID_ARGUMENT, "rows (%zu) must be a multiple of the combiner's jobs (%zu): job-major rows", rows, c->jobs);
     if (!d_status) return fail(SDA_ERR_INVALID_ARGUMENT, "d_status is NULL");
@@ -2731,15 +2789,8 @@ extern "C" int sda_share_combiner_update_varint_dev(sda_share_combiner_t* c, sda
     if (n_bytes > 0 && !d_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     const size_t L = c->dimension, stride = L + (L & 1), rows_per_job = rows / c->jobs;
     SDA_TRY(c->ctx.use());
-    if (varint_use_stream(rows)) {
-        // many rows: 16 rows of a job per workgroup, decoded values summed in an LDS column window - no decoded tile
-        const RowRanges rr{d_row_offsets, nullptr, 0};
-        SDA_TRY(c->join_pending(c->ctx.pick(stream)));
-        HIP_TRY(launch_varint_stream_combine(d_bytes, n_bytes, rr, c->jobs, rows_per_job, L, c->acc.lo.as<uint64_t>(),
-                                             c->acc.hi.as<int64_t>(), d_status, c->ctx.pick(stream)));
-        if (L == 0) HIP_TRY(launch_varint_stream_decode(d_bytes, n_bytes, rr, rows, 0, 0, nullptr, d_status, c->ctx.pick(stream)));
-        return c->mark_pending(c->ctx.pick(stream));
-    }
+    if (varint_use_stream(rows))         // many rows
+        return stream_combine(c, d_bytes, n_bytes, RowRanges{d_row_offsets, nullptr, 0}, rows, d_status, c->ctx.pick(stream));
     SDA_TRY(c->tile.reserve((rows * stride ? rows * stride : 1) * 8));
     SDA_TRY(sda_varint_decode_dev(codec, d_bytes, n_bytes, d_row_offsets, rows, L, c->tile.as<int64_t>(), stride, d_status, stream));
     if (L == 0) return SDA_OK;
@@ -2749,12 +2800,6 @@ extern "C" int sda_share_combiner_update_varint_dev(sda_share_combiner_t* c, sda
 // ---- slotted rows: row r at d_bytes + r*slot_bytes, d_row_bytes[r] bytes long (single-pass kernels only) ----------
 extern "C" size_t sda_varint_slot_size(size_t len) { return (len * 10 + 15) / 16 * 16; }
 
-static int check_slots(const void* d_bytes, size_t slot_bytes, size_t len) {
-    if (slot_bytes % 16 || ((uintptr_t)d_bytes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "slots must be 16-byte aligned (buffer and slot_bytes)");
-    if (slot_bytes < len * 10) return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < 10 * len (sda_varint_slot_size)");
-    return SDA_OK;
-}
-
 extern "C" int sda_varint_encode_rows_dev(sda_varint_codec_t* c, const int64_t* d_values, size_t rows, size_t len,
                                           size_t row_stride, uint8_t* d_out, size_t slot_bytes, uint64_t* d_row_bytes,
                                           void* stream) {
@@ -2762,7 +2807,8 @@ extern "C" int sda_varint_encode_rows_dev(sda_varint_codec_t* c, const int64_t* 
     if (rows == 0) return SDA_OK;
     if (!d_out || !d_row_bytes || (len > 0 && !d_values)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (row_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < len");
-    SDA_TRY(check_slots(d_out, slot_bytes, len));
+    SDA_TRY(check_slots("slots", d_out, slot_bytes));
+    if (slot_bytes < len * 10) return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < 10 * len (sda_varint_slot_size)");
     SDA_TRY(c->ctx.use());
     HIP_TRY(launch_varint_stream_encode(VarintRows{d_values, rows, len, row_stride}, d_out, slot_bytes, d_row_bytes, c->ctx.pick(stream)));
     return SDA_OK;
@@ -2775,7 +2821,7 @@ extern "C" int sda_varint_decode_rows_dev(sda_varint_codec_t* c, const uint8_t* 
     if (rows == 0) return SDA_OK;
     if (!d_bytes || !d_row_bytes || (len > 0 && !d_values)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (row_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < len");
-    if (slot_bytes % 16 || ((uintptr_t)d_bytes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "slots must be 16-byte aligned (buffer and slot_bytes)");
+    SDA_TRY(check_slots("slots", d_bytes, slot_bytes));
     SDA_TRY(c->ctx.use());
     HIP_TRY(launch_varint_stream_decode(d_bytes, rows * slot_bytes, RowRanges{nullptr, d_row_bytes, slot_bytes}, rows, len, row_stride,
                                         d_values, d_status, c->ctx.pick(stream)));
@@ -2785,21 +2831,13 @@ extern "C" int sda_varint_decode_rows_dev(sda_varint_codec_t* c, const uint8_t* 
 extern "C" int sda_share_combiner_update_varint_rows_dev(sda_share_combiner_t* c, sda_varint_codec_t* codec,
                                                          const uint8_t* d_bytes, size_t slot_bytes, const uint64_t* d_row_bytes,
                                                          size_t rows, uint32_t* d_status, void* stream) {
-    if (!c || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!c->begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    SDA_TRY(check_wire_fed(c && codec, true, c && c->begun, c && c->acc.rust_signed));
     if (rows == 0 || c->jobs == 0) return SDA_OK;
     if (rows % c->jobs) return fail(SDA_ERR_INVALID_ARGUMENT, "rows (%zu) must be a multiple of the combiner's jobs (%zu): job-major rows", rows, c->jobs);
     if (!d_status || !d_bytes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (slot_bytes % 16 || ((uintptr_t)d_bytes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "slots must be 16-byte aligned (buffer and slot_bytes)");
+    SDA_TRY(check_slots("slots", d_bytes, slot_bytes));
     SDA_TRY(c->ctx.use());
-    const RowRanges rr{nullptr, d_row_bytes, slot_bytes};
-    const size_t L = c->dimension;
-    SDA_TRY(c->join_pending(c->ctx.pick(stream)));
-    HIP_TRY(launch_varint_stream_combine(d_bytes, rows * slot_bytes, rr, c->jobs, rows / c->jobs, L, c->acc.lo.as<uint64_t>(),
-                                         c->acc.hi.as<int64_t>(), d_status, c->ctx.pick(stream)));
-    if (L == 0) HIP_TRY(launch_varint_stream_decode(d_bytes, rows * slot_bytes, rr, rows, 0, 0, nullptr, d_status, c->ctx.pick(stream)));
-    return c->mark_pending(c->ctx.pick(stream));
+    return stream_combine(c, d_bytes, rows * slot_bytes, RowRanges{nullptr, d_row_bytes, slot_bytes}, rows, d_status, c->ctx.pick(stream));
 }
 
 // a clerking job straight from its sealed boxes (clerk.rs:78-86): verify every tag, then ONE pass that decrypts, decodes and sums
@@ -2807,27 +2845,29 @@ extern "C" int sda_share_combiner_update_sealed_rows_dev(sda_share_combiner_t* c
                                                          const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes,
                                                          size_t slot_bytes, const uint64_t* d_row_bytes, size_t rows,
                                                          size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status, void* stream) {
-    if (!c || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!pk || !sk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!c->begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    SDA_TRY(check_wire_fed(c && codec && b, pk && sk, c && c->begun, c && c->acc.rust_signed));
     if (c->jobs != 1) return fail(SDA_ERR_STATE, "the sealed form feeds ONE job: the combiner was begun with %zu jobs", c->jobs);
     if (rows == 0) return SDA_OK;
-    if (!d_status || !d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    if (max_box_bytes > slot_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "max_box_bytes exceeds slot_bytes");
-    SDA_TRY(c->ctx.use());
-    hipStream_t s = c->ctx.pick(stream);
+    hipStream_t s = nullptr;
     const SboxState* d_states = nullptr;
-    SDA_TRY(capi_sealedbox_verify_rows(b, pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status, c->ctx.device, s,
-                                       &d_states));
+    SDA_TRY(sealed_rows_verify(c->ctx, b, pk, sk, SealedRows{d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_ok, d_status}, stream, &s,
+                               &d_states));
     SDA_TRY(c->join_pending(s));
     int waves = 0;
     HIP_TRY(launch_sealed_stream_combine(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, c->dimension,
                                          c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_status, s, &waves));
-    note_kernel("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);      // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_combine_kernel<%d>", waves);
     return c->mark_pending(s);
+}
+
+// the seal sequence over rows of values in HBM (a value is at most 10 bytes on the wire): shares here, the ChaCha kind's seed rows in
+// mask_sealed_rows_dev
+static int seal_share_rows(sda_sealedbox* b, const SealKeys& K, const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes,
+                           hipStream_t stream) {
+    return capi_sealedbox_seal(b, K, R.rows, R.len * 10, d_boxes, slot_bytes, d_row_bytes, stream, "share rows",
+                               [&](const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t s) {
+        return launch_varint_seal_stream(R, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    });
 }
 
 // a participation's share rows straight into sealed boxes (participate.rs:82-101): setup, ONE pass that encodes and encrypts, tags
@@ -2839,17 +2879,14 @@ extern "C" int sda_sealedbox_seal_share_rows_dev(sda_sealedbox_t* b, sda_varint_
     if (!pks || n_pks == 0 || rows_per_key == 0) return fail(SDA_ERR_INVALID_ARGUMENT, "bad recipient key arguments");
     if (!d_boxes || !d_row_bytes || (len > 0 && !d_values)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (row_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "row_stride < len");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    if (len > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(len) + SDA_SEALBYTES)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(len) + 48");
-    if (capi_sealedbox_device(b) != codec->ctx.device)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "the sealed-box handle lives on device %d, the codec on device %d", capi_sealedbox_device(b), codec->ctx.device);
+    SDA_TRY(check_slots("boxes", d_boxes, slot_bytes));
+    SDA_TRY(check_seal_room(slot_bytes, len, "len"));
+    SDA_TRY(check_one_device(b, codec->ctx.device));
     if (rows == 0) return SDA_OK;
     SDA_TRY(codec->ctx.use());
-    SDA_TRY(capi_sealedbox_seal_share_rows(b, pks, n_pks, rows_per_key, esk, VarintRows{d_values, rows, len, row_stride}, d_boxes, slot_bytes,
-                                           d_row_bytes, codec->ctx.pick(stream)));
-    note_kernel("varint_seal_stream_kernel + sbox_poly_kernel");                    // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    SDA_TRY(seal_share_rows(b, SealKeys{pks, n_pks, rows_per_key, esk}, VarintRows{d_values, rows, len, row_stride}, d_boxes, slot_bytes,
+                            d_row_bytes, codec->ctx.pick(stream)));
+    NOTE_CALL_KERNELS("varint_seal_stream_kernel + sbox_poly_kernel");
     return SDA_OK;
 }
 
@@ -2864,13 +2901,10 @@ extern "C" int sda_share_generator_generate_sealed_rows_dev(sda_share_generator_
     if (!pks) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL clerk keys");
     if (!d_boxes || !d_row_bytes || (len > 0 && !d_secrets)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (secrets_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "secrets_stride < len");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
+    SDA_TRY(check_slots("boxes", d_boxes, slot_bytes));
     const size_t B = (len + g->k - 1) / g->k;                     // values per row (additive: k = 1)
-    if (B > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(B) + SDA_SEALBYTES)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(batches) + 48");
-    if (capi_sealedbox_device(b) != codec->ctx.device || g->ctx.device != codec->ctx.device)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "the generator lives on device %d, the sealed-box handle on device %d, the codec on device %d",
-                    g->ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    SDA_TRY(check_seal_room(slot_bytes, B, "batches"));
+    SDA_TRY(check_one_device(b, codec->ctx.device, "generator", g->ctx.device));
     if (g->rust_signed)
         return fail(SDA_ERR_UNSUPPORTED, "the sealed form computes canonical shares only: SDA_VALUES_RUST_SIGNED takes generate_batch_dev + seal_share_rows_dev");
     if (!g->additive && g->k + g->t > 32)
@@ -2899,11 +2933,15 @@ extern "C" int sda_share_generator_generate_sealed_rows_dev(sda_share_generator_
     // like generate_batch_dev: nothing is drawn for an empty job, every other call runs under its own call key
     if (len > 0) J.key = g->drbg.call_key();
     g_last_gen_kernel[0] = 0;
-    const int st = capi_sealedbox_seal_generated_rows(b, pks, esk, J, g->drbg.rounds, d_boxes, slot_bytes, d_row_bytes, g->ctx.pick(stream));
+    // n keys, a key's rows are its clerk's: one per participant; a share is at most 10 bytes on the wire
+    const int st = capi_sealedbox_seal(b, SealKeys{pks, J.n, participants, esk}, rows, B * 10, d_boxes, slot_bytes, d_row_bytes,
+                                       g->ctx.pick(stream), "generated share rows",
+                                       [&](const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t s) {
+        return launch_share_seal_stream(J, g->drbg.rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    });
     explicit_bzero(&J.key, sizeof J.key);
     if (st != SDA_OK) return st;
-    note_kernel("share_seal_stream_kernel<%d> + sbox_poly_kernel", g->drbg.rounds);      // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    NOTE_CALL_KERNELS("share_seal_stream_kernel<%d> + sbox_poly_kernel", g->drbg.rounds);
     return SDA_OK;
 }
 
@@ -2925,48 +2963,29 @@ static int mask_sealed_rows_dev(sda_secret_masker_t* m, const uint32_t* seed_wor
     if (!pk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL recipient key");
     if (!d_boxes || !d_row_bytes || (len > 0 && (!d_secrets || !d_masked))) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
     if (secrets_stride < len || masked_stride < len) return fail(SDA_ERR_INVALID_ARGUMENT, "stride < len");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    const size_t mask_len = (size_t)sda_secret_masker_mask_len(m, len);
-    if (mask_len > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(mask_len) + SDA_SEALBYTES)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(sda_secret_masker_mask_len(len)) + 48");
-    if (capi_sealedbox_device(b) != codec->ctx.device || c.ctx.device != codec->ctx.device)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "the masker lives on device %d, the sealed-box handle on device %d, the codec on device %d",
-                    c.ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    SDA_TRY(check_slots("boxes", d_boxes, slot_bytes));
+    SDA_TRY(check_seal_room(slot_bytes, (size_t)sda_secret_masker_mask_len(m, len), "sda_secret_masker_mask_len(len)"));
+    SDA_TRY(check_one_device(b, codec->ctx.device, "masker", c.ctx.device));
     if (c.scheme.kind == SDA_MASKING_CHACHA) {                                // chacha.rs:24-54 for every participant
-        if (len != c.scheme.dimension)
-            return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (dimension %llu, secrets %zu) - chacha.rs:26",
-                        (unsigned long long)c.scheme.dimension, len);
+        SDA_TRY(check_chacha_dimension(c, len));
         if (participants == 0) return SDA_OK;
-        if (len) {                                                            // as mask_batch_dev: a repair writes a position a second time
-            const uintptr_t sec0 = reinterpret_cast<uintptr_t>(d_secrets), out0 = reinterpret_cast<uintptr_t>(d_masked);
-            const uintptr_t sec1 = sec0 + ((participants - 1) * secrets_stride + len) * 8, out1 = out0 + ((participants - 1) * masked_stride + len) * 8;
-            if (sec0 < out1 && out0 < sec1)
-                return fail(SDA_ERR_INVALID_ARGUMENT, "d_masked overlaps d_secrets: the ChaCha kind does not mask in place");
-        }
+        SDA_TRY(check_not_in_place(d_secrets, secrets_stride, d_masked, masked_stride, participants, len));
         SDA_TRY(c.ctx.use());
         hipStream_t s = c.ctx.pick(stream);
         const size_t nw = c.seed_words();
-        WipedVec<uint32_t> raw(participants * nw ? participants * nw : 1);
-        if (seed_words) memcpy(raw.data(), seed_words, participants * nw * 4);
-        else SDA_TRY(os_entropy(raw.data(), participants * nw * 4));
-        WipedVec<int64_t> words(participants * nw ? participants * nw : 1);
-        WipedVec<uint32_t> key8(participants * 8, 0u);
-        for (size_t p = 0; p < participants; ++p)
-            for (size_t i = 0; i < nw; ++i) {
-                words[p * nw + i] = (int64_t)raw[p * nw + i];
-                if (i < 8) key8[p * 8 + i] = raw[p * nw + i];
-            }
+        ChaChaSeeds seeds(participants, nw);
+        SDA_TRY(seeds.draw(seed_words));
         SDA_TRY(mask_chunk_scratch(c, participants, s));
         const size_t words_bytes = participants * nw * 8;
         SDA_TRY(c.d_words.reserve_wiped(words_bytes));
         const MaskApply apply{d_secrets, secrets_stride, d_masked, masked_stride, c.mod};
-        SDA_TRY(end_synchronised(s, [&]() -> int {                            // the host vectors above are in flight until it returns
+        SDA_TRY(end_synchronised(s, [&]() -> int {                            // `seeds` is in flight until it returns
             const int st = [&]() -> int {
-                if (words_bytes) HIP_TRY(hipMemcpyAsync(c.d_words.p, words.data(), words_bytes, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(c.d_seeds.p, key8.data(), participants * 32, hipMemcpyHostToDevice, s));
+                if (words_bytes) HIP_TRY(hipMemcpyAsync(c.d_words.p, seeds.words.data(), words_bytes, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(c.d_seeds.p, seeds.key8.data(), participants * 32, hipMemcpyHostToDevice, s));
                 SDA_TRY(chacha_expand(c, participants, false, len, &apply, s));
-                return capi_sealedbox_seal_share_rows(b, pk, 1, participants, esk, VarintRows{c.d_words.as<int64_t>(), participants, nw, nw},
-                                                      d_boxes, slot_bytes, d_row_bytes, s);
+                return seal_share_rows(b, SealKeys{pk, 1, participants, esk}, VarintRows{c.d_words.as<int64_t>(), participants, nw, nw},
+                                       d_boxes, slot_bytes, d_row_bytes, s);
             }();
             // whatever became of the call: the seed rows and their keys do not outlive it
             const hipError_t z0 = hipMemsetAsync(c.d_words.p, 0, c.d_words.cap, s), z1 = hipMemsetAsync(c.d_seeds.p, 0, participants * 32, s);
@@ -2975,8 +2994,7 @@ static int mask_sealed_rows_dev(sda_secret_masker_t* m, const uint32_t* seed_wor
             HIP_TRY(z1);
             return SDA_OK;
         }));
-        note_kernel("chacha_expand (apply) + varint_seal_stream_kernel + sbox_poly_kernel");
-        snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+        NOTE_CALL_KERNELS("chacha_expand (apply) + varint_seal_stream_kernel + sbox_poly_kernel");
         return SDA_OK;
     }
     // Full - full.rs:21-35
@@ -2988,11 +3006,15 @@ static int mask_sealed_rows_dev(sda_secret_masker_t* m, const uint32_t* seed_wor
     J.len = len; J.participants = participants; J.first_participant = first_participant; J.mod = c.mod;
     // like mask_batch_dev: nothing is drawn for empty rows, every other call runs under its own call key
     if (len > 0) J.key = c.drbg.call_key();
-    const int st = capi_sealedbox_seal_masked_rows(b, pk, esk, J, c.drbg.rounds, d_boxes, slot_bytes, d_row_bytes, c.ctx.pick(stream));
+    // one key, a row per participant; the encode pass draws the masks it encodes and stores the masked secrets
+    const int st = capi_sealedbox_seal(b, SealKeys{pk, 1, participants, esk}, participants, len * 10, d_boxes, slot_bytes, d_row_bytes,
+                                       c.ctx.pick(stream), "masked rows",
+                                       [&](const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t s) {
+        return launch_mask_seal_stream(J, c.drbg.rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    });
     explicit_bzero(&J.key, sizeof J.key);
     if (st != SDA_OK) return st;
-    note_kernel("mask_seal_stream_kernel<%d> + sbox_poly_kernel", c.drbg.rounds);      // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    NOTE_CALL_KERNELS("mask_seal_stream_kernel<%d> + sbox_poly_kernel", c.drbg.rounds);
     return SDA_OK;
 }
 
@@ -3027,15 +3049,12 @@ extern "C" int sda_share_combiner_finish_sealed_rows_dev(sda_share_combiner_t* c
     if (!c || !codec || !b) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
     if (!pk) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL recipient key");
     if (!d_boxes || !d_row_bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL device pointer");
-    if (slot_bytes % 16 || ((uintptr_t)d_boxes & 15u)) return fail(SDA_ERR_INVALID_ARGUMENT, "boxes must be 16-byte aligned (buffer and slot_bytes)");
-    if (capi_sealedbox_device(b) != codec->ctx.device || c->ctx.device != codec->ctx.device)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "the combiner lives on device %d, the sealed-box handle on device %d, the codec on device %d",
-                    c->ctx.device, capi_sealedbox_device(b), codec->ctx.device);
+    SDA_TRY(check_slots("boxes", d_boxes, slot_bytes));
+    SDA_TRY(check_one_device(b, codec->ctx.device, "combiner", c->ctx.device));
     if (!c->begun) return fail(SDA_ERR_STATE, "finish before begin");
     if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the sealed finish folds 128-bit sums: SDA_VALUES_RUST_SIGNED takes finish_dev + seal_share_rows_dev");
     const size_t L = c->dimension;
-    if (L > (SIZE_MAX - 64) / 10 || slot_bytes < sda_varint_slot_size(L) + SDA_SEALBYTES)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "slot_bytes < sda_varint_slot_size(dimension) + 48");
+    SDA_TRY(check_seal_room(slot_bytes, L, "dimension"));
     if (c->jobs == 0) return SDA_OK;
     SDA_TRY(c->ctx.use());
     hipStream_t s = c->ctx.pick(stream);
@@ -3045,18 +3064,23 @@ extern "C" int sda_share_combiner_finish_sealed_rows_dev(sda_share_combiner_t* c
     SDA_TRY(codec->d_aux.reserve(scan_aux_entries(nb) * 8));
     SDA_TRY(c->join_pending(s));
     const SumRows S{c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), c->jobs, L, c->mod.m, c->mod.mu};
-    SDA_TRY(capi_sealedbox_seal_summed_rows(b, pk, esk, S, codec->d_blocks.as<uint32_t>(), codec->d_offs.as<uint64_t>(),
-                                            codec->d_total.as<uint64_t>(), codec->d_aux.as<uint64_t>(), d_boxes, slot_bytes, d_row_bytes, s));
-    note_kernel("sum_len_kernel + sum_seal_wide_kernel + sbox_poly_kernel");         // the whole call, not only its last launch
-    snprintf(g_last_call_kernels, sizeof g_last_call_kernels, "%s", g_last_gen_kernel);
+    // one key, a row per job, every row split over the chip: block lengths, their scan, then the pass that reduces, encodes and encrypts
+    SDA_TRY(capi_sealedbox_seal(b, SealKeys{pk, 1, S.jobs, esk}, S.jobs, L * 10, d_boxes, slot_bytes, d_row_bytes, s, "summed rows",
+                                [&](const SboxState* d_states, uint64_t* d_msg_bytes, hipStream_t st) {
+        uint32_t* d_block_bytes = codec->d_blocks.as<uint32_t>();
+        uint64_t* d_block_off = codec->d_offs.as<uint64_t>();
+        hipError_t e = launch_sum_lengths(S, d_block_bytes, st);
+        if (e == hipSuccess && L) e = launch_scan_u32(d_block_bytes, d_block_off, nb, codec->d_total.as<uint64_t>(), codec->d_aux.as<uint64_t>(), st);
+        if (e == hipSuccess) e = launch_sum_seal_wide(S, d_block_off, d_boxes, slot_bytes, d_states, d_msg_bytes, st);
+        return e;
+    }));
+    NOTE_CALL_KERNELS("sum_len_kernel + sum_seal_wide_kernel + sbox_poly_kernel");
     return c->mark_pending(s);
 }
 
 extern "C" int sda_share_combiner_update_varint(sda_share_combiner_t* c, sda_varint_codec_t* codec, const uint8_t* bytes,
                                                 size_t n_bytes) {
-    if (!c || !codec) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (!c->begun) return fail(SDA_ERR_STATE, "update before begin");
-    if (c->acc.rust_signed) return fail(SDA_ERR_UNSUPPORTED, "the wire-fed updates sum in 128 bits: SDA_VALUES_RUST_SIGNED takes decode + update[_dev]");
+    SDA_TRY(check_wire_fed(c && codec, true, c && c->begun, c && c->acc.rust_signed));
     if (c->jobs != 1) return fail(SDA_ERR_STATE, "the host form takes one participant's vector for ONE job (begin with jobs == 1)");
     if (n_bytes > 0 && !bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL buffer");
     SDA_TRY(c->ctx.use());

@@ -118,16 +118,15 @@ extern "C" int sda_sealedbox_open_rows_dev(sda_sealedbox_t* b, const uint8_t pk[
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box open launch failed: %s", hipGetErrorString(e));
 }
 
-// for sda_share_combiner_update_sealed_rows_dev (sda_capi.cpp), which has checked the arguments
-int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const uint8_t* d_boxes, size_t slot_bytes,
-                               const uint64_t* d_row_bytes, size_t rows, size_t max_box_bytes, uint32_t* d_ok, uint32_t* d_status,
-                               int device, hipStream_t s, const SboxState** d_states) {
-    const size_t max_msg = max_box_bytes > SDA_SEALBYTES ? max_box_bytes - SDA_SEALBYTES : 0;
+// for the update_sealed_rows_dev entry points (sda_capi.cpp), which have checked the arguments
+int capi_sealedbox_verify_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t sk[32], const SealedRows& R, int device, hipStream_t s,
+                               const SboxState** d_states) {
+    const size_t max_msg = R.max_box_bytes > SDA_SEALBYTES ? R.max_box_bytes - SDA_SEALBYTES : 0;
     if (b->device != device) return capi_fail(SDA_ERR_INVALID_ARGUMENT, "the sealed-box handle lives on device %d, the combiner on device %d", b->device, device);
-    if (int st = scratch(b, rows, max_msg)) return st;
-    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
-    hipError_t e = launch_sealedbox_verify(pk, sk, d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, static_cast<uint64_t*>(b->d_lens),
-                                           d_ok, d_status, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
+    if (int st = scratch(b, R.rows, max_msg)) return st;
+    if (int st = reserve(b->d_lens, b->lens_cap, R.rows * sizeof(uint64_t), false)) return st;
+    hipError_t e = launch_sealedbox_verify(pk, sk, R.d_boxes, R.slot_bytes, R.d_row_bytes, R.rows, R.max_box_bytes, static_cast<uint64_t*>(b->d_lens),
+                                           R.d_ok, R.d_status, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
     *d_states = static_cast<const SboxState*>(b->d_states);
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box verify launch failed: %s", hipGetErrorString(e));
 }
@@ -150,93 +149,31 @@ extern "C" int sda_sealedbox_seal_rows_dev(sda_sealedbox_t* b, const uint8_t* pk
     if (int st = stage_keys(b, pks, n_pks, esk, rows, s, &d_esk, &d_pks)) return st;
     hipError_t e = launch_sealedbox_seal(d_esk, d_pks, n_pks, rows_per_key, d_msgs, msg_slot, d_msg_bytes, rows, max_msg_bytes, d_boxes,
                                          slot_bytes, d_row_bytes, static_cast<SboxState*>(b->d_states), static_cast<uint32_t*>(b->d_partial), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    const hipError_t wiped = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    if (e == hipSuccess) e = wiped;
     return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealed-box seal launch failed: %s", hipGetErrorString(e));
 }
 
-// for sda_sealedbox_seal_share_rows_dev (sda_capi.cpp), which has checked the arguments: setup, then ONE pass that encodes the rows
-// and encrypts them into the boxes, then the Poly1305 pass and the tags.  The message lengths the encode pass finds go through the
-// handle's d_lens; key staging and wiping as in seal_rows_dev.
-int capi_sealedbox_seal_share_rows(sda_sealedbox* b, const uint8_t* pks, size_t n_pks, size_t rows_per_key, const uint8_t* esk,
-                                   const VarintRows& R, uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
-    const size_t rows = R.rows, max_msg = R.len * 10;      // a share is at most 10 bytes on the wire
+// for the sealed-row producers of sda_capi.cpp, which have checked the arguments: THE seal sequence.  Setup, then the caller's
+// encode pass, which encodes the rows, encrypts them into the boxes and leaves the message lengths it found in the handle's d_lens,
+// then the Poly1305 pass and the tags.  Key staging as in seal_rows_dev; the ephemeral secrets are wiped whatever became of the
+// launches, and the status is that of the first failure.  what: the rows' name in the error text
+int capi_sealedbox_seal(sda_sealedbox* b, const SealKeys& K, size_t rows, size_t max_msg, uint8_t* d_boxes, size_t slot_bytes,
+                        uint64_t* d_row_bytes, hipStream_t s, const char* what, EncodePass encode) {
     if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
     if (int st = scratch(b, rows, max_msg)) return st;
     if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
     uint8_t *d_esk = nullptr, *d_pks = nullptr;
-    if (int st = stage_keys(b, pks, n_pks, esk, rows, s, &d_esk, &d_pks)) return st;
+    if (int st = stage_keys(b, K.pks, K.n_pks, K.esk, rows, s, &d_esk, &d_pks)) return st;
     SboxState* d_states = static_cast<SboxState*>(b->d_states);
     uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
-    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, n_pks, rows_per_key, d_boxes, slot_bytes, rows, d_states, s);
-    if (e == hipSuccess) e = launch_varint_seal_stream(R, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
+    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, K.n_pks, K.rows_per_key, d_boxes, slot_bytes, rows, d_states, s);
+    if (e == hipSuccess) e = encode(d_states, d_msg_bytes, s);
     if (e == hipSuccess)
         e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
-    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing share rows: launch failed: %s", hipGetErrorString(e));
-}
-
-// for sda_share_generator_generate_sealed_rows_dev (sda_capi.cpp), which has checked the arguments: as above, the encode pass
-// computing the rows it encodes
-int capi_sealedbox_seal_generated_rows(sda_sealedbox* b, const uint8_t* pks, const uint8_t* esk, const ShareJob& J, int rounds,
-                                       uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
-    const size_t rows = (size_t)J.n * J.participants, max_msg = (size_t)J.batches * 10;
-    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
-    if (int st = scratch(b, rows, max_msg)) return st;
-    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
-    uint8_t *d_esk = nullptr, *d_pks = nullptr;
-    if (int st = stage_keys(b, pks, J.n, esk, rows, s, &d_esk, &d_pks)) return st;
-    SboxState* d_states = static_cast<SboxState*>(b->d_states);
-    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
-    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, J.n, J.participants, d_boxes, slot_bytes, rows, d_states, s);
-    if (e == hipSuccess) e = launch_share_seal_stream(J, rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
-    if (e == hipSuccess)
-        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
-    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing generated share rows: launch failed: %s", hipGetErrorString(e));
-}
-
-// for sda_secret_masker_mask_sealed_rows_dev (sda_capi.cpp, the Full kind), which has checked the arguments: as above, the encode
-// pass drawing the masks it encodes and storing the masked secrets; one key, rows = participants
-int capi_sealedbox_seal_masked_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const MaskJob& J, int rounds,
-                                    uint8_t* d_boxes, size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
-    const size_t rows = J.participants, max_msg = J.len * 10;
-    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
-    if (int st = scratch(b, rows, max_msg)) return st;
-    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
-    uint8_t *d_esk = nullptr, *d_pks = nullptr;
-    if (int st = stage_keys(b, pk, 1, esk, rows, s, &d_esk, &d_pks)) return st;
-    SboxState* d_states = static_cast<SboxState*>(b->d_states);
-    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
-    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, 1, rows, d_boxes, slot_bytes, rows, d_states, s);
-    if (e == hipSuccess) e = launch_mask_seal_stream(J, rounds, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
-    if (e == hipSuccess)
-        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
-    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing masked rows: launch failed: %s", hipGetErrorString(e));
-}
-
-// for sda_share_combiner_finish_sealed_rows_dev (sda_capi.cpp), which has checked the arguments and reserved the scan scratch
-// (d_block_bytes / d_block_off: jobs * sum_seal_blocks(len) entries; d_scan_aux: scan_aux_entries of that; d_scan_total: 8 bytes):
-// as above with the rows computed from the clerk sums and every row split over the chip - lengths, scan, encode + encrypt
-int capi_sealedbox_seal_summed_rows(sda_sealedbox* b, const uint8_t pk[32], const uint8_t* esk, const SumRows& S, uint32_t* d_block_bytes,
-                                    uint64_t* d_block_off, uint64_t* d_scan_total, uint64_t* d_scan_aux, uint8_t* d_boxes,
-                                    size_t slot_bytes, uint64_t* d_row_bytes, hipStream_t s) {
-    const size_t rows = S.jobs, max_msg = S.len * 10;
-    if (hipSetDevice(b->device) != hipSuccess) return capi_fail(SDA_ERR_HIP, "hipSetDevice failed");
-    if (int st = scratch(b, rows, max_msg)) return st;
-    if (int st = reserve(b->d_lens, b->lens_cap, rows * sizeof(uint64_t), false)) return st;
-    uint8_t *d_esk = nullptr, *d_pks = nullptr;
-    if (int st = stage_keys(b, pk, 1, esk, rows, s, &d_esk, &d_pks)) return st;
-    SboxState* d_states = static_cast<SboxState*>(b->d_states);
-    uint64_t* d_msg_bytes = static_cast<uint64_t*>(b->d_lens);
-    hipError_t e = launch_sealedbox_seal_setup(d_esk, d_pks, 1, rows, d_boxes, slot_bytes, rows, d_states, s);
-    if (e == hipSuccess) e = launch_sum_lengths(S, d_block_bytes, s);
-    if (e == hipSuccess && S.len) e = launch_scan_u32(d_block_bytes, d_block_off, rows * sum_seal_blocks(S.len), d_scan_total, d_scan_aux, s);
-    if (e == hipSuccess) e = launch_sum_seal_wide(S, d_block_off, d_boxes, slot_bytes, d_states, d_msg_bytes, s);
-    if (e == hipSuccess)
-        e = launch_sealedbox_seal_auth(d_msg_bytes, rows, max_msg, d_boxes, slot_bytes, d_row_bytes, d_states, static_cast<uint32_t*>(b->d_partial), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
-    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing summed rows: launch failed: %s", hipGetErrorString(e));
+    const hipError_t wiped = hipMemsetAsync(d_esk, 0, rows * 32, s);                       // ephemeral secrets are single-use
+    if (e == hipSuccess) e = wiped;
+    return e == hipSuccess ? SDA_OK : capi_fail(SDA_ERR_HIP, "sealing %s: launch failed: %s", what, hipGetErrorString(e));
 }
 
 int capi_sealedbox_device(const sda_sealedbox* b) { return b->device; }

@@ -119,9 +119,19 @@ def test_chacha_dimension_and_state_checks(gpu):
     with pytest.raises(crypto.SdaError) as e:
         comb.begin_dev(99)
     assert e.value.code == capi.ERR_INVALID_ARGUMENT
+    pk, sk = _keys(40)
+    codec, box = crypto.VarintCodec(), crypto.SealedBox()
+
+    def sealed(d_boxes=d.ptr, slot=64, d_lens=d.ptr + 1024, rows=4, max_box=64, status=d.ptr + 2048):
+        comb.update_sealed_rows_dev(codec, box, pk, sk, d_boxes, slot, d_lens, rows, max_box, status)
+    with pytest.raises(crypto.SdaError) as e:
+        sealed()
+    assert e.value.code == capi.ERR_STATE
     comb.begin_dev(100)
+    sealed(d_boxes=0, rows=0)                                                  # rows == 0: nothing is looked at, nothing launched
     for call in (lambda: comb.update_dev(0, 1, 4, 4), lambda: comb.update_dev(d.ptr, 1, 4, 3), lambda: comb.finish_dev(d.ptr, 99),
-                 lambda: comb.finish_dev(0, 100)):
+                 lambda: comb.finish_dev(0, 100), lambda: sealed(d_boxes=0), lambda: sealed(d_lens=0), lambda: sealed(status=0),
+                 lambda: sealed(d_boxes=d.ptr + 8), lambda: sealed(slot=72), lambda: sealed(max_box=80)):
         with pytest.raises(crypto.SdaError) as e:
             call()
         assert e.value.code == capi.ERR_INVALID_ARGUMENT

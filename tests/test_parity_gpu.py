@@ -1461,6 +1461,10 @@ def test_device_entry_points_refuse_bad_arguments(gpu):
     assert lib.sda_share_combiner_update_varint_dev(c, v, buf.ptr, 100, None, 16, st.ptr, None) == bad
     assert lib.sda_share_combiner_update_varint_rows_dev(c, v, buf.ptr + 8, 64, buf.ptr, 8, st.ptr, None) == bad
     assert lib.sda_share_combiner_update_varint_rows_dev(c, v, buf.ptr, 40, buf.ptr, 8, st.ptr, None) == bad
+    assert lib.sda_share_combiner_update_varint_rows_dev(c, v, buf.ptr, 64, buf.ptr, 9, st.ptr, None) == bad
+    assert lib.sda_share_combiner_update_varint_rows_dev(c, v, buf.ptr, 64, buf.ptr, 8, None, None) == bad
+    assert lib.sda_share_combiner_update_varint_dev(c, v, buf.ptr, 100, buf.ptr, 16, None, None) == bad
+    assert lib.sda_share_combiner_update_varint_dev(c, v, None, 100, buf.ptr, 16, st.ptr, None) == bad
     assert lib.sda_varint_encode_rows_dev(v, buf.ptr, 2, 10, 10, buf.ptr + 1024, 96, buf.ptr + 2048, None) == bad       # slot < 10 * len
     assert lib.sda_varint_encode_rows_dev(v, buf.ptr, 2, 10, 9, buf.ptr + 1024, 112, buf.ptr + 2048, None) == bad       # stride < len
     assert lib.sda_varint_decode_dev(v, buf.ptr, 100, None, 3, 4, buf.ptr + 1024, 4, st.ptr, None) == bad              # offsets needed

@@ -274,9 +274,9 @@ def test_state_machine(gpu):
     d_rows, d_out, d_status = DeviceBuffer.from_numpy(b.rows), DeviceBuffer(case.dim + 1), DeviceBytes(4).zero()
     L = b.row_len
 
-    def sealed(first, n):
-        rec.update_sealed_rows_dev(codec, box, pk, sk, first, job.d_boxes.ptr + first * job.slot, job.slot, job.d_lens.ptr + 8 * first, n,
-                                   job.slot, d_status.ptr)
+    def sealed(first, n, d_boxes=job.d_boxes.ptr, slot=job.slot, max_box=job.slot, d_lens=job.d_lens.ptr, status=d_status.ptr):
+        rec.update_sealed_rows_dev(codec, box, pk, sk, first, d_boxes and d_boxes + first * job.slot, slot, d_lens and d_lens + 8 * first, n,
+                                   max_box, status)
     # update and finish before begin
     _raises(capi.ERR_STATE, lambda: rec.update_dev(0, d_rows.ptr, 1, L))
     _raises(capi.ERR_STATE, lambda: sealed(0, 1))
@@ -305,6 +305,9 @@ def test_state_machine(gpu):
         _raises(capi.ERR_STATE, lambda: sealed(3, 2))
         _raises(capi.ERR_INVALID_ARGUMENT, lambda: rec.update_dev(0, 0, 1, L))
         _raises(capi.ERR_INVALID_ARGUMENT, lambda: rec.update_dev(0, d_rows.ptr, 1, L - 1))
+        for kw in (dict(d_boxes=0), dict(d_lens=0), dict(status=0), dict(d_boxes=job.d_boxes.ptr + 8), dict(slot=job.slot + 8),
+                   dict(max_box=job.slot + 16)):                                          # one bad argument each, position 0 stays free
+            _raises(capi.ERR_INVALID_ARGUMENT, lambda: sealed(0, 1, **kw))
         sealed(2, 2)
         _raises(capi.ERR_STATE, lambda: rec.finish_dev(d_out.ptr, case.dim))              # position 0 is missing
         sealed(0, 1)
