@@ -512,6 +512,39 @@ int sda_secret_unmasker_unmask(sda_secret_unmasker_t* u,
 int sda_secret_unmasker_unmask_dev(sda_secret_unmasker_t* u, const int64_t* d_mask, const int64_t* d_masked, size_t len,
                                    int64_t* d_out, void* stream);
 
+/* unmask() fed by the recipient's two device jobs - the last step of reveal_aggregation, client/src/receive.rs:148-156, with
+ * neither of its operands in HBM.  `c` is a mask combiner job (begin_dev, updates of either form) and `r` a reconstructor job of
+ * the same shape, every position fed; the call ends both and writes the RecipientOutput's values.  With L the reconstructor
+ * job's output length (PackedShamir: dimension, Additive: row_len):
+ *     masked = fold of r's 128-bit sums mod q_share,   mask = fold of c's 128-bit sums mod q_mask,
+ *     d_out[i] = (canonical(masked[i], q_mask) - mask[i]) mod q_mask,   0 <= i < L
+ * bit for bit what sda_secret_reconstructor_finish_dev -> d_masked, sda_mask_combiner_finish_dev -> d_mask and
+ * sda_secret_unmasker_unmask_dev(u, d_mask, d_masked, L, d_out) give for the same two jobs.  The two moduli may differ: the
+ * reference subtracts under the masking scheme's modulus whatever the sharing modulus is (full.rs:60-63, chacha.rs:86-89), so
+ * both operands are canonicalised under q_mask.  The padding accumulators of the last packed batch are not written
+ * (batched.rs:94).  None (none.rs:28-33): d_out = masked; `c` may be NULL, or a None combiner whose job, if begun, is ended.
+ * ChaCha with no seed fed: the combined mask is `dimension` zeros (chacha.rs:58), d_out = masked.
+ *   ONE KERNEL reads both jobs' sums: no combined mask and no masked output is written to device memory, the call allocates
+ * nothing, does not synchronise and copies nothing to the host.  Everything is enqueued on `stream` (NULL: the default stream
+ * the handles use); the caller has ordered both jobs' updates before it, and the call counts as a use of each handle under its
+ * one-stream-at-a-time rule.  d_out needs 8-byte alignment only.
+ *   THE GATE: d_status_masks / d_status_results are optional device words - the d_status of the jobs' sealed updates.  Where one
+ * is given and is non-zero when the kernel runs, the kernel stores NOTHING to d_out: a reveal with one bad box produces no
+ * output, as in the reference (sodium.rs:78-80 fails the whole decrypt), without a host round trip between the updates and the
+ * finish.  The two may be the same word; NULL: no gate.  The call's status does not tell: the caller still reads the words
+ * afterwards.  The jobs are ended either way.
+ *   On SDA_OK both jobs are ended exactly as their own finish_dev ends them - another begin_dev may follow - and the mask
+ * combiner's key scratch is zeroed on the stream.  L == 0 is SDA_OK, launches nothing and ends the jobs.
+ *   REFUSALS, all before any launch, both jobs left as they were: NULL u or r, NULL c with a kind other than None, NULL d_out
+ * with L > 0, out_cap < L, u and c built from different masking schemes (kind, modulus, for ChaCha the dimension), the three
+ * handles not on one device -> SDA_ERR_INVALID_ARGUMENT; either job not begun, or a reconstructor position not fed (the text of
+ * finish_dev) -> SDA_ERR_STATE; Full / ChaCha with a mask job dimension other than L -> SDA_ERR_ASSERTION (assert_eq!,
+ * full.rs:58, chacha.rs:83); SDA_VALUES_RUST_SIGNED on the unmasker or read into either job at its begin_dev ->
+ * SDA_ERR_UNSUPPORTED - the three-call chain serves it, as for every wire-fed form. */
+int sda_secret_unmasker_unmask_jobs_dev(sda_secret_unmasker_t* u, sda_mask_combiner_t* c, sda_secret_reconstructor_t* r,
+                                        const uint32_t* d_status_masks, const uint32_t* d_status_results, int64_t* d_out,
+                                        size_t out_cap, void* stream);
+
 /* RecipientOutput::positive - client/src/receive.rs:13-21: v < 0 ? v + modulus : v.  Host-side,
  * element-wise; the identity on this library's canonical outputs. */
 int sda_positive(const int64_t* values, size_t len, int64_t modulus, int64_t* out);

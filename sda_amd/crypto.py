@@ -324,10 +324,8 @@ class ShareCombiner(_Handle):
         """begin_dev(1, dimension) + update_sealed_rows_dev over an SDAJOBv1 blob of sealed boxes, its failures raised as the
         reference's; returns the number of rows (0: nothing was begun)"""
         from .device import DeviceBuffer, DeviceBytes
-        job = JobContainer.parse(bytes(blob))
+        job = _parse_sealed_job(what, blob)
         L = job.layout
-        if L.payload_kind != capi.JOB_SEALED:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{what} needs a job of sealed boxes (payload kind SEALED)")
         if L.rows == 0:
             return 0
         d_job = DeviceBytes.from_bytes(job.blob)
@@ -335,13 +333,7 @@ class ShareCombiner(_Handle):
         self.begin_dev(1, dimension)
         self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes, d_job.ptr + L.lengths_offset,
                                     L.rows, L.slot_bytes, d_status.ptr)
-        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
-        if status & 16:
-            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
-        if status & 2:
-            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")                    # combiner.rs:21
-        if status:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        _raise_sealed_status(int(d_status.to_numpy()[0]))
         return L.rows
 
     def combine_sealed_job(self, blob, pk: bytes, sk: bytes, dimension: int) -> np.ndarray:
@@ -394,6 +386,25 @@ class ShareCombiner(_Handle):
 
     def finish_dev(self, d_out: int, stream: int = 0):
         check(self._lib.sda_share_combiner_finish_dev(self._h, d_out, stream or None))
+
+
+def _parse_sealed_job(what: str, blob) -> "JobContainer":
+    """an SDAJOBv1 blob that must hold sealed boxes"""
+    job = JobContainer.parse(bytes(blob))
+    if job.layout.payload_kind != capi.JOB_SEALED:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{what} needs a job of sealed boxes (payload kind SEALED)")
+    return job
+
+
+def _raise_sealed_status(status: int) -> None:
+    """the status word of a sealed update as the reference's errors, in their order of precedence"""
+    status &= 0xFFFFFFFF
+    if status & 16:
+        raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
+    if status & 2:
+        raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")                    # combiner.rs:21
+    if status:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
 
 
 class SecretReconstructor(_Handle):
@@ -459,32 +470,38 @@ class SecretReconstructor(_Handle):
         """receive.rs:120-146 for an SDAJOBv1 blob of sealed clerking results, row i from clerk indices[i]: open every one,
         reconstruct.  One bad box fails the reveal ("Sodium decryption failure"), so does a payload that does not hold
         row_len values (default: ceil(dimension / k); Additive: the dimension)."""
-        from .device import DeviceBuffer, DeviceBytes
-        job = JobContainer.parse(bytes(blob))
-        L = job.layout
-        if L.payload_kind != capi.JOB_SEALED:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, "reconstruct_sealed_job needs a job of sealed boxes (payload kind SEALED)")
+        from .device import DeviceBuffer
+        job = _parse_sealed_job("reconstruct_sealed_job", blob)
+        row_len, n_out = self._sealed_job_shape(row_len)
+        d_out = DeviceBuffer(max(n_out, 1))
+        d_status = DeviceBuffer(1).zero()
+        held = self._feed_sealed_job(job, indices, row_len, pk, sk, d_status.ptr)
+        self.finish_dev(d_out.ptr, n_out)
+        _raise_sealed_status(int(d_status.to_numpy()[0]))
+        del held
+        return d_out.to_numpy()[:n_out].copy()
+
+    def _sealed_job_shape(self, row_len: Optional[int]) -> Tuple[int, int]:
+        """(values per sealed clerking result, output length) of a job on this handle; row_len None: the scheme's own"""
         additive = isinstance(self.scheme, Additive)
         if row_len is None:
             row_len = self.dimension if additive else -(-self.dimension // self.scheme.secret_count)
-        n_out = row_len if additive else self.dimension
-        d_out = DeviceBuffer(max(n_out, 1))
-        d_status = DeviceBuffer(1).zero()
-        self.begin_dev(None if additive else indices, L.rows, row_len)
-        if L.rows:
-            d_job = DeviceBytes.from_bytes(job.blob)
-            codec, box = VarintCodec(), SealedBox()
-            self.update_sealed_rows_dev(codec, box, pk, sk, 0, d_job.ptr + L.payload_offset, L.slot_bytes,
-                                        d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status.ptr)
-        self.finish_dev(d_out.ptr, n_out)
-        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
-        if status & 16:
-            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
-        if status & 2:
-            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")
-        if status:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
-        return d_out.to_numpy()[:n_out].copy()
+        return row_len, (row_len if additive else self.dimension)
+
+    def _feed_sealed_job(self, job: "JobContainer", indices: Optional[Sequence[int]], row_len: int, pk: bytes, sk: bytes,
+                         d_status: int):
+        """begin_dev + update_sealed_rows_dev over a parsed SDAJOBv1 SEALED job, row i from clerk indices[i]; the failures of
+        the boxes land in *d_status.  Returns what must stay alive until the job's stream work is done"""
+        from .device import DeviceBytes
+        L = job.layout
+        self.begin_dev(None if isinstance(self.scheme, Additive) else indices, L.rows, row_len)
+        if not L.rows:
+            return None
+        d_job = DeviceBytes.from_bytes(job.blob)
+        codec, box = VarintCodec(), SealedBox()
+        self.update_sealed_rows_dev(codec, box, pk, sk, 0, d_job.ptr + L.payload_offset, L.slot_bytes,
+                                    d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status)
+        return d_job, codec, box
 
 
 # ---- masking -------------------------------------------------------------------------------------------------
@@ -597,32 +614,37 @@ class MaskCombiner(_Handle):
         box fails the job ("Sodium decryption failure"), so does a payload that is no varint vector.  ChaCha: the result
         has the scheme's dimension (chacha.rs:58); Full: `dimension` is the length every mask must have ("Wrong dimension"
         otherwise)."""
-        from .device import DeviceBuffer, DeviceBytes
-        job = JobContainer.parse(bytes(blob))
-        L = job.layout
-        if L.payload_kind != capi.JOB_SEALED:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, "combine_sealed_job needs a job of sealed boxes (payload kind SEALED)")
-        if isinstance(self.scheme, ChaCha):
-            dimension = self.scheme.dimension
-        elif dimension is None:
-            raise ValueError("combine_sealed_job needs the masks' dimension for this scheme")
+        from .device import DeviceBuffer
+        job = _parse_sealed_job("combine_sealed_job", blob)
+        dimension = self._sealed_job_dimension(dimension)
         d_out = DeviceBuffer(max(dimension, 1))
         d_status = DeviceBuffer(1).zero()
-        self.begin_dev(dimension)
-        if L.rows:
-            d_job = DeviceBytes.from_bytes(job.blob)
-            codec, box = VarintCodec(), SealedBox()
-            self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes,
-                                        d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status.ptr)
+        held = self._feed_sealed_job(job, dimension, pk, sk, d_status.ptr)
         self.finish_dev(d_out.ptr, dimension)
-        status = int(d_status.to_numpy()[0]) & 0xFFFFFFFF
-        if status & 16:
-            raise SdaError(capi.ERR_SODIUM_DECRYPTION, "Sodium decryption failure")        # sodium.rs:80
-        if status & 2:
-            raise SdaError(capi.ERR_WRONG_DIMENSION, "Wrong dimension")
-        if status:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
+        _raise_sealed_status(int(d_status.to_numpy()[0]))
+        del held
         return d_out.to_numpy()[:dimension].copy()
+
+    def _sealed_job_dimension(self, dimension: Optional[int]) -> int:
+        if isinstance(self.scheme, ChaCha):
+            return self.scheme.dimension
+        if dimension is None:
+            raise ValueError("combine_sealed_job needs the masks' dimension for this scheme")
+        return dimension
+
+    def _feed_sealed_job(self, job: "JobContainer", dimension: int, pk: bytes, sk: bytes, d_status: int):
+        """begin_dev + update_sealed_rows_dev over a parsed SDAJOBv1 SEALED job of mask encryptions; the failures of the boxes
+        land in *d_status.  Returns what must stay alive until the job's stream work is done"""
+        from .device import DeviceBytes
+        L = job.layout
+        self.begin_dev(dimension)
+        if not L.rows:
+            return None
+        d_job = DeviceBytes.from_bytes(job.blob)
+        codec, box = VarintCodec(), SealedBox()
+        self.update_sealed_rows_dev(codec, box, pk, sk, d_job.ptr + L.payload_offset, L.slot_bytes,
+                                    d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status)
+        return d_job, codec, box
 
 
 class SecretUnmasker(_Handle):
@@ -645,6 +667,16 @@ class SecretUnmasker(_Handle):
 
     def unmask_dev(self, d_mask: int, d_masked: int, length: int, d_out: int, stream: int = 0) -> None:
         check(self._lib.sda_secret_unmasker_unmask_dev(self._h, d_mask or None, d_masked, length, d_out, stream or None))
+
+    def unmask_jobs_dev(self, combiner: Optional["MaskCombiner"], reconstructor: "SecretReconstructor", d_out: int, out_cap: int,
+                        d_status_masks: int = 0, d_status_results: int = 0, stream: int = 0) -> None:
+        """the recipient's last step (receive.rs:148-156) from the two device jobs' sums: what reconstructor.finish_dev,
+        combiner.finish_dev and unmask_dev give, in one kernel, with neither the combined mask nor the masked output in HBM.
+        Ends both jobs.  d_status_*: the status words of the jobs' sealed updates as gates - one of them non-zero when the
+        kernel runs and nothing is stored to d_out.  combiner None: a None unmasker only"""
+        _check_mask(self._lib.sda_secret_unmasker_unmask_jobs_dev(
+            self._h, combiner._h if combiner is not None else None, reconstructor._h if reconstructor is not None else None,
+            d_status_masks or None, d_status_results or None, d_out or None, out_cap, stream or None))
 
 
 # ---- factory (client/src/crypto/mod.rs:58-66) ---------------------------------------------------------------
@@ -766,6 +798,46 @@ def participate_sealed(aggregation: Aggregation, secrets_2d, recipient_pk: bytes
     generator.generate_sealed_rows_dev(codec, box, clerk_pks, d_ptr, P, length, length, d_boxes.ptr, slot, d_lens.ptr,
                                        first_participant, share_esk)
     return mask_job, jobs_of(d_boxes, d_lens, slot, n)
+
+
+def reveal_sealed(aggregation: Aggregation, mask_job, result_job, indices: Optional[Sequence[int]], recipient_pk: bytes,
+                  recipient_sk: bytes) -> RecipientOutput:
+    """reveal_aggregation (receive.rs:80-157) from wire bytes, the counterpart of participate_sealed and
+    ShareCombiner.clerk_sealed_job: mask_job is the SDAJOBv1 SEALED blob of the participants' mask encryptions (None for
+    NoMask), result_job the one of the clerking results, row i from clerk indices[i] (Additive: indices may be None).  Both jobs
+    are fed from the sealed boxes, then SecretUnmasker.unmask_jobs_dev folds and unmasks their sums with both status words as
+    gates; the words and the output come back in one copy.  One bad box fails the reveal ("Sodium decryption failure"), then
+    "Wrong dimension", then a malformed varint stream, whichever of the two jobs it came from."""
+    from .device import DeviceBuffer
+    a = aggregation
+    sch, msch = a.committee_sharing_scheme, a.masking_scheme
+    if len(recipient_pk) != 32 or len(recipient_sk) != 32:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
+    if msch.has_mask() != (mask_job is not None):
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
+    masks = _parse_sealed_job("reveal_sealed", mask_job) if mask_job is not None else None
+    results = _parse_sealed_job("reveal_sealed", result_job)
+    additive = isinstance(sch, Additive)
+    if not additive and (indices is None or len(indices) != results.layout.rows):
+        raise SdaError(capi.ERR_INVALID_ARGUMENT,
+                       f"{0 if indices is None else len(indices)} indices for {results.layout.rows} clerking results")
+    if additive and indices is not None and len(indices) != results.layout.rows:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {results.layout.rows} clerking results")
+    reconstructor = SecretReconstructor(sch, a.vector_dimension)
+    row_len, n_out = reconstructor._sealed_job_shape(None)
+    unmasker = SecretUnmasker(msch)
+    combiner = MaskCombiner(msch) if masks is not None else None
+    # [0]: the mask job's status word, [1]: the clerking results', [2 ..): the output, 16-byte aligned
+    d_buf = DeviceBuffer(2 + max(n_out, 1)).zero()
+    held = []
+    if combiner is not None:                 # ChaCha: the scheme's dimension; one that is not n_out is the reference's assert_eq! (chacha.rs:83)
+        held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
+    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1)))
+    unmasker.unmask_jobs_dev(combiner, reconstructor, d_buf.at(2), n_out, d_buf.at(0), d_buf.at(1))
+    back = d_buf.to_numpy()
+    del held
+    _raise_sealed_status(int(back[0]) | int(back[1]))
+    return RecipientOutput(a.modulus, back[2:2 + n_out].copy())
 
 
 # ---- share-vector wire codec (SURVEY.md 8f rank 1) -------------------------------------------------------------

@@ -238,6 +238,14 @@ hipError_t launch_packed_reconstruct_n31(const int64_t* d_shares, size_t row_str
 // out = (a + b) mod m   or   (a - b) mod m, any i64 inputs
 hipError_t launch_addsub_mod(const int64_t* d_a, const int64_t* d_b, size_t len, bool subtract,
                              const ModParams& mod, int64_t* d_out, hipStream_t s);
+// unmask (full.rs:54-67, chacha.rs:79-93, none.rs:28-33) fed by the recipient's two device jobs: out[i] = (fold of the
+// reconstructor job's sums mod recon_mod, canonicalised under mask_mod) - (fold of the mask job's sums mod mask_mod), mod mask_mod,
+// i < len.  d_mask_lo == nullptr: no mask, out = the fold of the reconstructor's sums.  The accumulator arrays hold at least `len`
+// entries and are 16-byte aligned; d_out any 8-byte aligned pointer.  d_gate_a / d_gate_b (nullptr: none): device words read when
+// the kernel starts - one of them non-zero and nothing is stored
+hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_recon_hi, const ModParams& recon_mod,
+                                const uint64_t* d_mask_lo, const int64_t* d_mask_hi, const ModParams& mask_mod, size_t len,
+                                const uint32_t* d_gate_a, const uint32_t* d_gate_b, int64_t* d_out, hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

@@ -2602,6 +2602,53 @@ extern "C" int sda_secret_unmasker_unmask_dev(sda_secret_unmasker_t* u, const in
     return c.addsub(d_masked, d_mask, len, true, d_out, c.ctx.pick(stream));
 }
 
+// unmask() fed by the recipient's two device jobs (receive.rs:148-156): what reconstructor_finish_dev + mask_combiner_finish_dev +
+// unmask_dev give, from one kernel that reads both jobs' sums - no combined mask and no masked output in HBM, nothing allocated.
+// Every refusal comes before the first launch and leaves both jobs as they were
+extern "C" int sda_secret_unmasker_unmask_jobs_dev(sda_secret_unmasker_t* u, sda_mask_combiner_t* mc, sda_secret_reconstructor_t* r,
+                                                   const uint32_t* d_status_masks, const uint32_t* d_status_results, int64_t* d_out,
+                                                   size_t out_cap, void* stream) {
+    if (!u) return fail(SDA_ERR_INVALID_ARGUMENT, "unmasker is NULL");
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    const MaskCore& uc = u->core;
+    const bool has_mask = uc.scheme.kind != SDA_MASKING_NONE;
+    if (!mc && has_mask) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL: only a None unmasker goes without one");
+    if (mc) {
+        const sda_masking_scheme_t &a = uc.scheme, &b = mc->core.scheme;
+        if (a.kind != b.kind || (has_mask && a.modulus != b.modulus) || (a.kind == SDA_MASKING_CHACHA && a.dimension != b.dimension))
+            return fail(SDA_ERR_INVALID_ARGUMENT, "the unmasker and the mask combiner were built from different masking schemes");
+    }
+    if (has_mask && (uc.ctx.device != r->ctx.device || mc->core.ctx.device != r->ctx.device))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the unmasker lives on device %d, the mask combiner on device %d, the reconstructor on device %d",
+                    uc.ctx.device, mc->core.ctx.device, r->ctx.device);
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "unmask before the reconstructor's begin");
+    if (has_mask && !mc->core.begun) return fail(SDA_ERR_STATE, "unmask before the mask combiner's begin");
+    if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
+    if (uc.rust_signed || r->job_acc.rust_signed || (has_mask && mc->core.acc.rust_signed))
+        return fail(SDA_ERR_UNSUPPORTED, "unmask_jobs_dev reads 128-bit sums: SDA_VALUES_RUST_SIGNED takes finish_dev + finish_dev + unmask_dev");
+    const size_t len = r->job_out;
+    if (has_mask && mc->core.job_dimension != len)                            // full.rs:58, chacha.rs:83
+        return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (mask %zu, masked secrets %zu)", mc->core.job_dimension, len);
+    if (len > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_cap < len) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    if (len) {
+        // the padding of the last batch is summed like every output and not written (batched.rs:94)
+        const AccState* m = has_mask ? &mc->core.acc : nullptr;
+        HIP_TRY(launch_unmask_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->mod, m ? m->lo.as<uint64_t>() : nullptr,
+                                     m ? m->hi.as<int64_t>() : nullptr, has_mask ? mc->core.mod : r->mod, len, d_status_masks,
+                                     d_status_results, d_out, s));
+        NOTE_CALL_KERNELS("unmask_finish_kernel");
+    }
+    if (mc) {                                                                 // as sda_mask_combiner_finish_dev ends its job
+        if (has_mask && mc->core.d_seeds.p) HIP_TRY(hipMemsetAsync(mc->core.d_seeds.p, 0, mc->core.d_seeds.cap, s));
+        mc->core.begun = false;
+    }
+    r->job_begun = false;
+    return SDA_OK;
+}
+
 extern "C" int sda_positive(const int64_t* values, size_t len, int64_t modulus, int64_t* out) {
     if (len && (!values || !out)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL buffer");
     // receive.rs:15 - `if v < 0 { v + modulus } else { v }`, no validation there either; formed in unsigned arithmetic so that a

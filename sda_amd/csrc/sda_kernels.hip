@@ -1164,6 +1164,96 @@ __global__ __launch_bounds__(kThreads) void combine_finish_kernel(const uint64_t
     out[i] = (int64_t)mod_i128(acc_lo[i], acc_hi[i], mod.m, mod.mu);
 }
 
+// The recipient's last step (receive.rs:148-156) straight from the two jobs' sums: the reconstructor job's accumulators folded
+// mod q_share (combine_finish_kernel's fold), the mask job's mod q_mask, then addsub_mod_kernel's subtraction under q_mask with
+// both operands canonicalised - neither the masked output nor the combined mask is written anywhere.  One lane = two adjacent
+// elements, the four accumulator arrays fetched 16 bytes at a time (they are library allocations: 16-byte aligned).
+// mod_i128 is bit-serial; the lane's folds are independent chains and step through ONE loop, so that the compare-subtract of one
+// can issue behind the shift of another.  A fold here is mod_i128 split in two: fold_head its sign handling and the reduction of
+// the high word, fold_step one of its 64 steps.
+struct FoldState {
+    uint64_t ml, r;
+    bool neg;
+};
+static __device__ __forceinline__ FoldState fold_head(uint64_t lo, int64_t hi, const ModParams& mod) {
+    FoldState f;
+    f.neg = hi < 0;
+    uint64_t mh = (uint64_t)hi;
+    f.ml = lo;
+    if (f.neg) {                                          // magnitude = -(hi:lo)
+        f.ml = ~f.ml + 1;
+        mh = ~mh + (f.ml == 0 ? 1u : 0u);
+    }
+    f.r = barrett_mod64(mh, mod.m, mod.mu);
+    return f;
+}
+static __device__ __forceinline__ void fold_step(FoldState& f, int bit, uint64_t m) {
+    f.r = (f.r << 1) | ((f.ml >> bit) & 1u);
+    if (f.r >= m) f.r -= m;
+}
+static __device__ __forceinline__ uint64_t fold_tail(const FoldState& f, uint64_t m) { return (f.neg && f.r != 0) ? m - f.r : f.r; }
+
+typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+
+// gate_a / gate_b: status words of the two jobs' sealed updates (nullptr: none).  One of them non-zero when the kernel starts =
+// a box failed to open: nothing is stored (sodium.rs:78-80 fails the whole reveal).  has_mask, vec_store and the gates are
+// wave-uniform.  vec_store: out is 16-byte aligned
+__global__ __launch_bounds__(kThreads) void unmask_finish_kernel(const uint64_t* __restrict__ r_lo, const int64_t* __restrict__ r_hi,
+                                                                 ModParams r_mod, const uint64_t* __restrict__ m_lo,
+                                                                 const int64_t* __restrict__ m_hi, ModParams m_mod, bool has_mask,
+                                                                 size_t len, const uint32_t* __restrict__ gate_a,
+                                                                 const uint32_t* __restrict__ gate_b, int64_t* __restrict__ out,
+                                                                 bool vec_store) {
+    if (gate_a && *gate_a != 0) return;
+    if (gate_b && *gate_b != 0) return;
+    const size_t i0 = 2 * ((size_t)blockIdx.x * kThreads + threadIdx.x);
+    if (i0 >= len) return;
+    const bool pair = i0 + 1 < len;                       // the odd tail reads and stores one element
+    ull2 rl{0, 0}, ml{0, 0};
+    ll2 rh{0, 0}, mh{0, 0};
+    if (pair) {
+        rl = *reinterpret_cast<const ull2*>(r_lo + i0);
+        rh = *reinterpret_cast<const ll2*>(r_hi + i0);
+    } else {
+        rl.x = r_lo[i0]; rh.x = r_hi[i0];
+    }
+    uint64_t o0, o1;
+    if (has_mask) {
+        if (pair) {
+            ml = *reinterpret_cast<const ull2*>(m_lo + i0);
+            mh = *reinterpret_cast<const ll2*>(m_hi + i0);
+        } else {
+            ml.x = m_lo[i0]; mh.x = m_hi[i0];
+        }
+        FoldState a0 = fold_head(rl.x, rh.x, r_mod), a1 = fold_head(rl.y, rh.y, r_mod);
+        FoldState b0 = fold_head(ml.x, mh.x, m_mod), b1 = fold_head(ml.y, mh.y, m_mod);
+        for (int bit = 63; bit >= 0; --bit) {
+            fold_step(a0, bit, r_mod.m); fold_step(b0, bit, m_mod.m);
+            fold_step(a1, bit, r_mod.m); fold_step(b1, bit, m_mod.m);
+        }
+        // the reference subtracts under the masking scheme's modulus whatever the sharing modulus is (full.rs:60-63,
+        // chacha.rs:86-89): a masked value may be >= q_mask
+        const uint64_t x0 = canon_i64((int64_t)fold_tail(a0, r_mod.m), m_mod.m, m_mod.mu);
+        const uint64_t x1 = canon_i64((int64_t)fold_tail(a1, r_mod.m), m_mod.m, m_mod.mu);
+        o0 = submod(x0, fold_tail(b0, m_mod.m), m_mod.m);
+        o1 = submod(x1, fold_tail(b1, m_mod.m), m_mod.m);
+    } else {                                              // none.rs:28-33: the masked output is the output
+        FoldState a0 = fold_head(rl.x, rh.x, r_mod), a1 = fold_head(rl.y, rh.y, r_mod);
+        for (int bit = 63; bit >= 0; --bit) {
+            fold_step(a0, bit, r_mod.m); fold_step(a1, bit, r_mod.m);
+        }
+        o0 = fold_tail(a0, r_mod.m);
+        o1 = fold_tail(a1, r_mod.m);
+    }
+    if (pair && vec_store) {
+        ll2 v; v.x = (long long)o0; v.y = (long long)o1;
+        *reinterpret_cast<ll2*>(out + i0) = v;
+    } else {
+        out[i0] = (int64_t)o0;
+        if (pair) out[i0 + 1] = (int64_t)o1;
+    }
+}
+
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
 // =================================================================================================
@@ -2267,6 +2357,19 @@ hipError_t launch_combine_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_
     const uint64_t blocks = ceil_div(count, kThreads);
     if (hipError_t e = grid_check(blocks)) return e;
     combine_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_acc_lo, d_acc_hi, count, mod, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_recon_hi, const ModParams& recon_mod,
+                                const uint64_t* d_mask_lo, const int64_t* d_mask_hi, const ModParams& mask_mod, size_t len,
+                                const uint32_t* d_gate_a, const uint32_t* d_gate_b, int64_t* d_out, hipStream_t s) {
+    if (len == 0) return hipSuccess;
+    const uint64_t blocks = ceil_div(ceil_div(len, 2), kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    const bool has_mask = d_mask_lo != nullptr;
+    unmask_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_recon_lo, d_recon_hi, recon_mod, d_mask_lo, d_mask_hi,
+                                                                           has_mask ? mask_mod : recon_mod, has_mask, len, d_gate_a,
+                                                                           d_gate_b, d_out, aligned16(d_out));
     return hipGetLastError();
 }
 

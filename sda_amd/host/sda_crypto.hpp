@@ -489,6 +489,36 @@ struct SecretUnmasker {
     }
 };
 
+/// The recipient's last step (receive.rs:148-156) for a MaskCombiner job and a SecretReconstructor job, both begun and fed on the
+/// device, through ONE call (sda_secret_unmasker_unmask_jobs_dev): their sums are folded and unmasked by one kernel, neither the
+/// combined mask nor the masked output is written to device memory, and both jobs are ended.  out_len: the reconstructor job's
+/// output length (PackedShamir: its dimension; Additive: row_len).  d_status_masks / d_status_results: the status words of the
+/// jobs' sealed updates (device pointers, may be null or equal) - they gate the kernel's stores, and one that is non-zero
+/// afterwards fails the reveal here with the reference's "Sodium decryption failure" (sodium.rs:80).  combiner: null for a None
+/// unmasker only.
+inline std::vector<Secret> unmask_jobs(SecretUnmasker& unmasker, MaskCombiner* combiner, SecretReconstructor& reconstructor, size_t out_len,
+                                       const uint32_t* d_status_masks = nullptr, const uint32_t* d_status_results = nullptr,
+                                       void* stream = nullptr) {
+    struct Dev {                                                    // freed on every way out
+        void* p = nullptr;
+        ~Dev() { if (p) sda_dev_free(p); }
+    } d_out;
+    detail::check(sda_dev_malloc(&d_out.p, out_len * sizeof(Secret) + 16));
+    detail::check(sda_secret_unmasker_unmask_jobs_dev(unmasker.h, combiner ? combiner->h : nullptr, reconstructor.h, d_status_masks,
+                                                      d_status_results, static_cast<int64_t*>(d_out.p), out_len, stream));
+    detail::check(sda_dev_synchronize());
+    for (const uint32_t* d_status : {d_status_masks, d_status_results}) {
+        uint32_t status = 0;
+        if (d_status) detail::check(sda_dev_download(&status, d_status, sizeof status));
+        if (status & 16) throw SdaClientError(SDA_ERR_SODIUM_DECRYPTION, "Sodium decryption failure");
+        if (status & 2) throw SdaClientError(SDA_ERR_WRONG_DIMENSION, "Wrong dimension");
+        if (status) throw SdaClientError(SDA_ERR_INVALID_ARGUMENT, "malformed varint stream");
+    }
+    std::vector<Secret> out(out_len);
+    if (out_len) detail::check(sda_dev_download(out.data(), d_out.p, out_len * sizeof(Secret)));
+    return out;
+}
+
 // ---- client/src/crypto/mod.rs:58-66 + the six *Construction traits ---------------------------------
 struct CryptoModule {
     std::unique_ptr<ShareGenerator> new_share_generator(const LinearSecretSharingScheme& s) const { return std::make_unique<ShareGenerator>(s); }
