@@ -411,6 +411,65 @@ int sda_secret_reconstructor_update_dev(sda_secret_reconstructor_t* r, size_t fi
                                         size_t row_stride, void* stream);
 int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r, int64_t* d_out, size_t out_cap, void* stream);
 
+/* The CHECKED streaming job (PackedShamir): the recipient learns from the rows it already holds whether the clerking results agree
+ * with each other, and which clerk to distrust.  Reconstruction needs t + k rows; the r = n_rows - (t + k) surplus rows are a
+ * Reed-Solomon redundancy that reconstruct() interpolates through and throws away.  With x_i = omega_shares^(indices[i] + 1), the
+ * node 1 (value 0) and u_i = 1 / prod_{l != i} (x_i - x_l) over all n_rows + 1 nodes, every batch b of rows that lie on one sharing
+ * polynomial (degree <= t + k) has
+ *     S_d[b] = sum_i u_i * x_i^d * share_i[b] = 0 (mod p),   d = 0 .. r - 1.
+ * begin_checked_dev puts `checks` of these sums behind the k secret columns of the job's matrix ([n_rows][k + checks]), so
+ * update_dev and update_sealed_rows_dev - unchanged, any mix, any order - stream the rows ONCE and sum the syndromes with the
+ * secrets; finish_checked_dev folds, tests and (on request) corrects.
+ *
+ *   begin_checked_dev : every check of begin_dev, in its order and with its errors (SDA_ERR_NOT_ENOUGH_SHARES, NULL indices,
+ *               SDA_ERR_ASSERTION for a short row_len (batched.rs:84), SDA_ERR_UNSUPPORTED above 65535 rows, colliding indices);
+ *               Additive -> SDA_ERR_UNSUPPORTED (there is no redundancy); checks == 0, checks > SDA_RECONSTRUCT_MAX_CHECKS or
+ *               checks > n_rows - (t + k) -> SDA_ERR_INVALID_ARGUMENT, which includes n_rows == t + k: nothing is checkable.  A
+ *               refused call leaves a job in flight as it was; one that passes replaces it.  MAY SYNCHRONISE the stream (the
+ *               matrix and two tables - R[s][i] / u_i and x_i - are built on the host and uploaded); zeroes
+ *               ceil(dimension / k) * (k + checks) 128-bit accumulators.  The sealed update picks its coefficient path (LDS up to
+ *               16 columns, memory above) by the job's width k + checks.
+ *   finish_checked_dev : an unfed position -> SDA_ERR_STATE; a policy other than the two, a NULL d_out / d_report or out_cap <
+ *               dimension -> SDA_ERR_INVALID_ARGUMENT.  Everything is enqueued on the stream: NO SYNCHRONISATION AND NO COPY TO
+ *               THE HOST.  d_report (device, sda_reconstruct_report_words(n_rows) = 4 + n_rows words) is initialised by the
+ *               call.  One kernel; per batch, the padding of the last batch included (it is checked like any batch and not
+ *               stored, batched.rs:94): a batch is BAD when a syndrome is non-zero; with checks >= 2 and S_0 != 0 it is LOCATED
+ *               when exactly one position i has S_{d+1} = x_i * S_d for every d < checks - 1; with checks == 1 bad batches are
+ *               counted and none is located or corrected.
+ *                 SDA_CHECK_REPORT : d_out[0 .. dimension) is bit for bit finish_dev's for the same rows.
+ *                 SDA_CHECK_CORRECT: a located batch's k secrets lose (R[s][i] / u_i) * S_0 - bit for bit what
+ *                                    sda_secret_reconstructor_reconstruct returns for the other n_rows - 1 rows; every other
+ *                                    batch as under SDA_CHECK_REPORT.
+ *               d_report: [0] bad batches, [1] located batches, [2] corrected batches, [3] the first bad batch (2^64 - 1: none),
+ *               [4 + i] batches that blame POSITION i (the position in `indices`, not the clerk index).  Sums and a minimum: the
+ *               report is deterministic.  Ends the job.
+ *   Mixing the two kinds: finish_dev on a checked job and finish_checked_dev on a plain job -> SDA_ERR_STATE,
+ *               sda_secret_unmasker_unmask_jobs_dev on a checked job -> SDA_ERR_UNSUPPORTED; the job stays as it was.
+ *   reconstruct_checked : the host form, with reconstruct's row-length rules and errors (n_rows < t + k, a row shorter than
+ *               ceil(dimension / k)): uploads the rows, runs begin_checked_dev + update_dev + finish_checked_dev (replacing a job
+ *               in flight on the handle), downloads out[0 .. dimension) and report (host, 4 + n_rows words).
+ *
+ *   What the syndromes guarantee (Reed-Solomon limits), per batch, with `checks` syndromes: 1 .. checks faulty rows are always
+ *   DETECTED; 2 .. checks - 1 faulty rows are never attributed to a single position (a Vandermonde argument), so they are never
+ *   mis-corrected; checks or more faulty rows MAY be attributed to one - possibly innocent - position and mis-corrected, and more
+ *   than checks may go unnoticed.  Values that differ by a multiple of p are the same share: clean.  Values past
+ *   ceil(dimension / k) of a row are not checked.
+ *   A clerking result whose box was refused by the sealed update adds nothing to the sums: it shows up here as a blamed position.
+ *   That does NOT replace checking *d_status of the sealed updates: the reference fails the whole reveal on such a box
+ *   (sodium.rs:78-80), whatever the other rows say. */
+#define SDA_RECONSTRUCT_MAX_CHECKS 16
+#define SDA_CHECK_REPORT  0   /* output = finish_dev's for the same rows, bit for bit */
+#define SDA_CHECK_CORRECT 1   /* a batch located to exactly one position is corrected */
+size_t sda_reconstruct_report_words(size_t n_rows);              /* 4 + n_rows */
+int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows,
+                                               size_t row_len, unsigned checks, void* stream);
+int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
+                                                uint64_t* d_report, void* stream);
+int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                 const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                 unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
+                                                 uint64_t* report /* host, sda_reconstruct_report_words(n_rows) */);
+
 /* =============================================================================================
  * SecretMasker / MaskCombiner / SecretUnmasker  (masking/mod.rs:9-31; impl none.rs, full.rs, chacha.rs)
  * ============================================================================================= */

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -407,6 +407,25 @@ def _raise_sealed_status(status: int) -> None:
         raise SdaError(capi.ERR_INVALID_ARGUMENT, f"malformed varint stream (status {status})")
 
 
+class RevealCheck(NamedTuple):
+    """the report of a checked reconstruction: batches with a non-zero syndrome, those located to exactly one position, those
+    corrected, the first bad batch (None: none) and, per POSITION of the index set, the batches that blame it"""
+    bad: int
+    located: int
+    corrected: int
+    first_bad: Optional[int]
+    blame: Tuple[int, ...]
+
+    @property
+    def clean(self) -> bool:
+        return self.bad == 0
+
+    @classmethod
+    def from_words(cls, words: Sequence[int]) -> "RevealCheck":
+        w = [int(x) & 0xFFFFFFFFFFFFFFFF for x in words]
+        return cls(w[0], w[1], w[2], None if w[3] == 0xFFFFFFFFFFFFFFFF else w[3], tuple(w[4:]))
+
+
 class SecretReconstructor(_Handle):
     """sharing/mod.rs:31-33; impl additive.rs:55-73 | batched.rs:68-97 + packed_shamir.rs:73-77."""
     _free = "sda_secret_reconstructor_free"
@@ -465,6 +484,58 @@ class SecretReconstructor(_Handle):
     def finish_dev(self, d_out: int, out_cap: int, stream: int = 0) -> None:
         check(self._lib.sda_secret_reconstructor_finish_dev(self._h, d_out or None, out_cap, stream or None))
 
+    # the checked job (PackedShamir): the surplus rows as parity checks - which clerking result disagrees with the others
+    def default_checks(self, n_rows: int) -> int:
+        """min(n_rows - (t + k), 4): what checks=None asks for"""
+        return min(n_rows - (self.scheme.privacy_threshold + self.scheme.secret_count), 4)
+
+    def begin_checked_dev(self, indices: Sequence[int], n_rows: int, row_len: int, checks: int, stream: int = 0) -> None:
+        """begin_dev with `checks` parity columns behind the k secret columns; update_dev / update_sealed_rows_dev feed it"""
+        if indices is not None and len(indices) != n_rows:
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {n_rows} rows")
+        cidx = None if indices is None else (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
+        check(self._lib.sda_secret_reconstructor_begin_checked_dev(self._h, cidx, n_rows, row_len, checks, stream or None))
+
+    def finish_checked_dev(self, d_out: int, out_cap: int, d_report: int, correct: bool = False, stream: int = 0) -> None:
+        """folds, tests the syndromes, locates, corrects on request; d_report: 4 + n_rows device words (RevealCheck.from_words).
+        Nothing synchronises or reaches the host"""
+        check(self._lib.sda_secret_reconstructor_finish_checked_dev(self._h, capi.CHECK_CORRECT if correct else capi.CHECK_REPORT,
+                                                                    d_out or None, out_cap, d_report or None, stream or None))
+
+    def reconstruct_checked(self, indexed_shares: Sequence[Tuple[int, Sequence]], checks: Optional[int] = None,
+                            correct: bool = False) -> Tuple[np.ndarray, "RevealCheck"]:
+        """reconstruct() that also says whether the rows agree: (values, RevealCheck)"""
+        idx = [int(i) for i, _ in indexed_shares]
+        arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
+        cidx = (C.c_size_t * max(len(idx), 1))(*idx)
+        if checks is None and not isinstance(self.scheme, Additive):
+            checks = self.default_checks(len(arrs))
+        out = np.empty(max(self.dimension, 1), dtype=np.int64)
+        report = (C.c_uint64 * (4 + len(arrs)))()
+        n_out = C.c_size_t()
+        check(self._lib.sda_secret_reconstructor_reconstruct_checked(
+            self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0), capi.CHECK_CORRECT if correct else capi.CHECK_REPORT,
+            _ptr(out), self.dimension, C.byref(n_out), report))
+        return out[:n_out.value].copy(), RevealCheck.from_words(list(report))
+
+    def reconstruct_sealed_job_checked(self, blob, indices: Sequence[int], pk: bytes, sk: bytes, checks: Optional[int] = None,
+                                       correct: bool = False) -> Tuple[np.ndarray, "RevealCheck"]:
+        """reconstruct_sealed_job with the checks riding along: (values, RevealCheck).  A bad box still fails the reveal
+        (sodium.rs:78-80) - the check is for results that open and disagree"""
+        from .device import DeviceBuffer
+        job = _parse_sealed_job("reconstruct_sealed_job_checked", blob)
+        row_len, n_out = self._sealed_job_shape(None)
+        rows = job.layout.rows
+        checks = self.default_checks(rows) if checks is None else checks
+        # [0]: the status word, [1 .. 5 + rows): the report, then the output
+        d_buf = DeviceBuffer(1 + 4 + rows + max(n_out, 1)).zero()
+        held = self._feed_sealed_job(job, indices, row_len, pk, sk, d_buf.at(0), checks=checks)
+        self.finish_checked_dev(d_buf.at(5 + rows), n_out, d_buf.at(1), correct)
+        back = d_buf.to_numpy()
+        del held
+        _raise_sealed_status(int(back[0]))
+        return back[5 + rows:5 + rows + n_out].copy(), RevealCheck.from_words(back[1:5 + rows].view(np.uint64).tolist())
+
     def reconstruct_sealed_job(self, blob, indices: Optional[Sequence[int]], pk: bytes, sk: bytes,
                                row_len: Optional[int] = None) -> np.ndarray:
         """receive.rs:120-146 for an SDAJOBv1 blob of sealed clerking results, row i from clerk indices[i]: open every one,
@@ -489,12 +560,16 @@ class SecretReconstructor(_Handle):
         return row_len, (row_len if additive else self.dimension)
 
     def _feed_sealed_job(self, job: "JobContainer", indices: Optional[Sequence[int]], row_len: int, pk: bytes, sk: bytes,
-                         d_status: int):
-        """begin_dev + update_sealed_rows_dev over a parsed SDAJOBv1 SEALED job, row i from clerk indices[i]; the failures of
-        the boxes land in *d_status.  Returns what must stay alive until the job's stream work is done"""
+                         d_status: int, checks: Optional[int] = None):
+        """begin_dev (checks given: begin_checked_dev) + update_sealed_rows_dev over a parsed SDAJOBv1 SEALED job, row i from
+        clerk indices[i]; the failures of the boxes land in *d_status.  Returns what must stay alive until the job's stream work
+        is done"""
         from .device import DeviceBytes
         L = job.layout
-        self.begin_dev(None if isinstance(self.scheme, Additive) else indices, L.rows, row_len)
+        if checks is None:
+            self.begin_dev(None if isinstance(self.scheme, Additive) else indices, L.rows, row_len)
+        else:
+            self.begin_checked_dev(indices, L.rows, row_len, checks)
         if not L.rows:
             return None
         d_job = DeviceBytes.from_bytes(job.blob)
@@ -838,6 +913,52 @@ def reveal_sealed(aggregation: Aggregation, mask_job, result_job, indices: Optio
     del held
     _raise_sealed_status(int(back[0]) | int(back[1]))
     return RecipientOutput(a.modulus, back[2:2 + n_out].copy())
+
+
+def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
+                          recipient_sk: bytes, checks: Optional[int] = None, correct: bool = False):
+    """reveal_sealed for a packed sharing scheme with the clerking results checked against each other: the results' job carries
+    `checks` parity columns (None: min(n_rows - (t + k), 4)), and the reveal is the chain MaskCombiner.finish_dev +
+    SecretReconstructor.finish_checked_dev + SecretUnmasker.unmask_dev - the one-kernel unmask_jobs_dev reads a plain job only.
+    Returns (RecipientOutput, RevealCheck); correct=True repairs every batch that one clerking result alone spoils.  The failures of
+    reveal_sealed stay: a bad box fails the reveal whatever the check says (sodium.rs:78-80)."""
+    from .device import DeviceBuffer
+    a = aggregation
+    sch, msch = a.committee_sharing_scheme, a.masking_scheme
+    if len(recipient_pk) != 32 or len(recipient_sk) != 32:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
+    if msch.has_mask() != (mask_job is not None):
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
+    masks = _parse_sealed_job("reveal_sealed_checked", mask_job) if mask_job is not None else None
+    results = _parse_sealed_job("reveal_sealed_checked", result_job)
+    if isinstance(sch, Additive):
+        raise SdaError(capi.ERR_UNSUPPORTED, "additive sharing has no redundancy to check")
+    rows = results.layout.rows
+    if indices is None or len(indices) != rows:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{0 if indices is None else len(indices)} indices for {rows} clerking results")
+    reconstructor = SecretReconstructor(sch, a.vector_dimension)
+    row_len, n_out = reconstructor._sealed_job_shape(None)
+    checks = reconstructor.default_checks(rows) if checks is None else checks
+    unmasker = SecretUnmasker(msch)
+    combiner = MaskCombiner(msch) if masks is not None else None
+    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 6 + rows): the report, then the masked output, the
+    # combined mask and the output
+    cap = max(n_out, 1)
+    d_buf = DeviceBuffer(6 + rows + 3 * cap).zero()
+    d_masked, d_mask, d_out = (d_buf.at(6 + rows + i * cap) for i in range(3))
+    held = []
+    if combiner is not None:
+        held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
+        combiner.finish_dev(d_mask, n_out)
+    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks))
+    reconstructor.finish_checked_dev(d_masked, n_out, d_buf.at(2), correct)
+    unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
+    back = d_buf.to_numpy()
+    del held
+    _raise_sealed_status(int(back[0]) | int(back[1]))
+    first = 6 + rows + 2 * cap
+    return (RecipientOutput(a.modulus, back[first:first + n_out].copy()),
+            RevealCheck.from_words(back[2:6 + rows].view(np.uint64).tolist()))
 
 
 # ---- share-vector wire codec (SURVEY.md 8f rank 1) -------------------------------------------------------------

@@ -246,6 +246,14 @@ hipError_t launch_addsub_mod(const int64_t* d_a, const int64_t* d_b, size_t len,
 hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_recon_hi, const ModParams& recon_mod,
                                 const uint64_t* d_mask_lo, const int64_t* d_mask_hi, const ModParams& mask_mod, size_t len,
                                 const uint32_t* d_gate_a, const uint32_t* d_gate_b, int64_t* d_out, hipStream_t s);
+// the finish of a checked reconstruction job: accumulators [batches][k + checks] (k secrets, then `checks` syndromes, 1 .. 16),
+// d_corr [k][n_rows] = R[s][i] / u_i and d_xs [n_rows] = the evaluation points, both in Montgomery form.  Per batch: fold, test
+// the syndromes, locate (exactly one position i with S_{d+1} = x_i S_d for every d < checks - 1; checks == 1 locates nothing),
+// under `correct` subtract corr[s][i] S_0, store d_out[b k + s] for b k + s < dimension.  d_report [4 + n_rows], initialised by
+// the caller to {0, 0, 0, 2^64 - 1, 0 ...}: bad, located, corrected batches, first bad batch, batches that blame position i
+hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                      uint32_t k, uint32_t checks, uint32_t n_rows, bool correct, size_t batches, size_t dimension,
+                                      const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

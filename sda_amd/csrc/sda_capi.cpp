@@ -1724,8 +1724,13 @@ struct sda_secret_reconstructor {
     bool job_begun = false;
     size_t job_rows = 0, job_row_len = 0, job_fed = 0, job_out = 0;
     std::vector<uint8_t> job_seen;       // positions already fed
+    // a CHECKED job (begin_checked_dev): job_checks parity columns ride behind the k secret columns - d_Rt is [n_rows][k + job_checks],
+    // the sums [batches][k + job_checks] - and finish_checked_dev reads the two tables.  0: a plain job
+    uint32_t job_checks = 0;
+    DevBuf d_corr, d_xs, d_report;       // [k][n_rows] R[s][i] / u_i and [n_rows] x_i, Montgomery form; reconstruct_checked's report
+    std::vector<uint64_t> h_R;           // d_R's content (have_R), for the tables of a checked job
     WeightedJob job() const {
-        return WeightedJob{d_Rt.as<uint64_t>(), k, (uint64_t)((dimension + k - 1) / k), mod.m, mod.mu, mont.pinv};
+        return WeightedJob{d_Rt.as<uint64_t>(), k + job_checks, (uint64_t)((dimension + k - 1) / k), mod.m, mod.mu, mont.pinv};
     }
 };
 
@@ -1766,7 +1771,7 @@ extern "C" void sda_secret_reconstructor_free(sda_secret_reconstructor_t* r) {
     if (!r) return;
     if (r->ctx.device >= 0) (void)hipSetDevice(r->ctx.device);
     r->acc.release(); r->tile.release(); r->d_out.release(); r->d_R.release(); r->d_R31.release(); r->d_shares.release();
-    r->job_acc.release(); r->d_Rt.release();
+    r->job_acc.release(); r->d_Rt.release(); r->d_corr.release(); r->d_xs.release(); r->d_report.release();
     r->ctx.destroy();
     delete r;
 }
@@ -1819,6 +1824,7 @@ static int prepare_R(sda_secret_reconstructor* r, const size_t* indices, size_t 
     if (ce != hipSuccess || se != hipSuccess)
         return fail(SDA_ERR_HIP, "uploading the reconstruction matrix failed: %s", hipGetErrorString(ce != hipSuccess ? ce : se));
     r->cached_indices.assign(indices, indices + n_rows);
+    r->h_R = std::move(R);
     r->have_R = true;
     return SDA_OK;
 }
@@ -1915,6 +1921,7 @@ extern "C" int sda_secret_reconstructor_begin_dev(sda_secret_reconstructor_t* r,
     hipStream_t s = r->ctx.pick(stream);
     if (!r->additive) SDA_TRY(prepare_R(r, indices, n_rows, s));            // colliding indices are refused here
     r->job_begun = false;                     // every argument check has passed: from here on a job in flight is replaced
+    r->job_checks = 0;
     if (!r->additive) {
         SDA_TRY(r->d_Rt.reserve((size_t)r->k * n_rows * 8));
         HIP_TRY(launch_transpose_u64(r->d_R.as<uint64_t>(), r->d_Rt.as<uint64_t>(), r->k, (uint32_t)n_rows, s));
@@ -1981,7 +1988,7 @@ extern "C" int sda_secret_reconstructor_update_sealed_rows_dev(sda_secret_recons
     } else {
         HIP_TRY(launch_sealed_stream_weighted(d_boxes, slot_bytes, d_row_bytes, rows, max_box_bytes, d_states, r->job_row_len, first_pos,
                                               r->job(), r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), d_status, s));
-        NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_weighted_kernel<8, %s>", r->k <= 16 ? "lds" : "global");
+        NOTE_CALL_KERNELS("sbox_poly_kernel + sealed_stream_weighted_kernel<8, %s>", r->k + r->job_checks <= 16 ? "lds" : "global");   // the job's width
     }
     return job_claim(r, first_pos, rows, true);
 }
@@ -1989,6 +1996,7 @@ extern "C" int sda_secret_reconstructor_update_sealed_rows_dev(sda_secret_recons
 extern "C" int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r, int64_t* d_out, size_t out_cap, void* stream) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
     if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_checked_dev: finish_checked_dev ends it");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
     if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
     if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
@@ -1996,6 +2004,130 @@ extern "C" int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r
     // the padding of the last batch is summed like every output and not written (batched.rs:94)
     if (r->job_out) SDA_TRY(acc_finish(r->job_acc, r->job_out, r->mod, d_out, r->ctx.pick(stream)));
     r->job_begun = false;
+    return SDA_OK;
+}
+
+// ---- the checked job: the n' - (t + k) surplus rows as a Reed-Solomon redundancy ---------------------------------------------
+// The sharing polynomial has degree <= t + k and the value 0 at the node 1, so with u_i = 1 / prod_{l != i} (x_i - x_l) over all
+// n' + 1 nodes (x_i = w3^(idx_i + 1); h_lagrange_matrix_mont's den_inv) every batch of clean rows has
+//     S_d = sum_i u_i x_i^d share_i = 0 mod p,   d = 0 .. n' - (t + k) - 1.
+// The job's matrix gets these weights as `checks` extra columns, [n_rows][k + checks], and the update kernels - which take the
+// width at run time - sum the syndromes next to the secrets in the one pass over the rows.  One faulty position c with error e:
+// S_d = u_c x_c^d e, and the all-rows reconstruction is off by R[s][c] e = (R[s][c] / u_c) S_0: the correction table.
+extern "C" size_t sda_reconstruct_report_words(size_t n_rows) { return 4 + n_rows; }
+
+extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows,
+                                                          size_t row_len, unsigned checks, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
+    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");       // packed_shamir.rs:75
+    if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
+    const size_t batches = (r->dimension + r->k - 1) / r->k;                 // batched.rs:77
+    if (row_len < batches) return fail(SDA_ERR_ASSERTION, "share vector shorter than the number of batches (index out of bounds, batched.rs:84)");
+    if (n_rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows");
+    const size_t surplus = n_rows - ((size_t)r->t + r->k);
+    if (checks == 0 || checks > SDA_RECONSTRUCT_MAX_CHECKS || checks > surplus)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u: 1 .. min(%d, n_rows - (t + k) = %zu) parity checks are possible", checks,
+                    SDA_RECONSTRUCT_MAX_CHECKS, surplus);
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    SDA_TRY(prepare_R(r, indices, n_rows, s));                               // colliding indices are refused here
+    // the tables, on the host: everything that can fail comes before the job in flight is touched
+    const uint64_t p = r->mod.m;
+    const uint64_t w3 = h_canon(r->scheme.omega_shares, p);
+    const uint32_t k = r->k, width = r->k + checks;
+    std::vector<uint64_t> x(n_rows), Rt(n_rows * (size_t)width), corr((size_t)k * n_rows), xs(n_rows);
+    for (size_t i = 0; i < n_rows; ++i) x[i] = h_powmod(w3, (uint64_t)indices[i] + 1, p);
+    for (size_t i = 0; i < n_rows; ++i) {
+        uint64_t den = submod(x[i], 1, p), u;                                // the node 1 first
+        for (size_t l = 0; l < n_rows; ++l)
+            if (l != i) den = h_mulmod(den, submod(x[i], x[l], p), p);
+        if (!h_invmod(den, p, u)) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstruction matrix is singular");
+        uint64_t h = h_to_mont(u, p);                                        // u_i x_i^d, Montgomery form
+        for (uint32_t e = 0; e < k; ++e) {
+            Rt[i * width + e] = r->h_R[(size_t)e * n_rows + i];
+            corr[(size_t)e * n_rows + i] = h_mulmod(r->h_R[(size_t)e * n_rows + i], den, p);   // (R 2^64) / u_i
+        }
+        for (unsigned d = 0; d < checks; ++d) {
+            Rt[i * width + k + d] = h;
+            h = h_mulmod(h, x[i], p);
+        }
+        xs[i] = h_to_mont(x[i], p);
+    }
+    r->job_begun = false;                     // every argument check has passed: from here on a job in flight is replaced
+    r->job_checks = 0;
+    SDA_TRY(r->d_Rt.reserve(Rt.size() * 8));
+    SDA_TRY(r->d_corr.reserve(corr.size() * 8));
+    SDA_TRY(r->d_xs.reserve(xs.size() * 8));
+    r->job_acc.rust_signed = false;           // packed Shamir has no signed mode (set_value_mode refuses it)
+    r->job_acc.q = r->acc.q;
+    SDA_TRY(r->job_acc.reset(batches * width, s));
+    hipError_t ce = hipMemcpyAsync(r->d_Rt.p, Rt.data(), Rt.size() * 8, hipMemcpyHostToDevice, s);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(r->d_corr.p, corr.data(), corr.size() * 8, hipMemcpyHostToDevice, s);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(r->d_xs.p, xs.data(), xs.size() * 8, hipMemcpyHostToDevice, s);
+    const hipError_t se = hipStreamSynchronize(s);                           // always: the tables are local vectors
+    if (ce != hipSuccess || se != hipSuccess)
+        return fail(SDA_ERR_HIP, "uploading the checked job's tables failed: %s", hipGetErrorString(ce != hipSuccess ? ce : se));
+    r->job_seen.assign(n_rows, 0);
+    r->job_rows = n_rows; r->job_row_len = row_len; r->job_fed = 0; r->job_out = r->dimension;
+    r->job_checks = checks;
+    r->job_begun = true;
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
+                                                           uint64_t* d_report, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
+    if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
+    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
+    if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (!d_report) return fail(SDA_ERR_INVALID_ARGUMENT, "d_report is NULL");
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    HIP_TRY(hipMemsetAsync(d_report, 0, sda_reconstruct_report_words(r->job_rows) * 8, s));
+    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, 8, s));                       // no bad batch yet
+    const size_t batches = (r->dimension + r->k - 1) / r->k;
+    HIP_TRY(launch_reveal_check_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                       r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows, policy == SDA_CHECK_CORRECT,
+                                       batches, r->dimension, r->mod, r->mont, d_out, d_report, s));
+    NOTE_CALL_KERNELS("reveal_check_finish_kernel");
+    r->job_begun = false;
+    r->job_checks = 0;
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                            const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                            unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
+                                                            uint64_t* report) {
+    if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_len = 0;
+    if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
+    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
+    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
+    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
+    const size_t batches = (r->dimension + r->k - 1) / r->k;
+    for (size_t i = 0; i < n_rows; ++i)
+        if (row_lens[i] < batches) return fail(SDA_ERR_ASSERTION, "share vector %zu shorter than the number of batches (index out of bounds, batched.rs:84)", i);
+    if (batches > 0 && (!out || out_cap < r->dimension)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(r->ctx.use());
+    const size_t stride = batches + (batches & 1), words = sda_reconstruct_report_words(n_rows);
+    SDA_TRY(r->d_shares.reserve(n_rows * stride * 8));
+    SDA_TRY(r->d_out.reserve(r->dimension * 8));
+    SDA_TRY(r->d_report.reserve(words * 8));
+    for (size_t i = 0; i < n_rows && batches; ++i)
+        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
+    SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
+    SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
+    SDA_TRY(sda_secret_reconstructor_finish_checked_dev(r, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
+    if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    SDA_TRY(r->ctx.sync());
+    *out_len = r->dimension;
     return SDA_OK;
 }
 
@@ -2622,6 +2754,7 @@ extern "C" int sda_secret_unmasker_unmask_jobs_dev(sda_secret_unmasker_t* u, sda
         return fail(SDA_ERR_INVALID_ARGUMENT, "the unmasker lives on device %d, the mask combiner on device %d, the reconstructor on device %d",
                     uc.ctx.device, mc->core.ctx.device, r->ctx.device);
     if (!r->job_begun) return fail(SDA_ERR_STATE, "unmask before the reconstructor's begin");
+    if (r->job_checks) return fail(SDA_ERR_UNSUPPORTED, "unmask_jobs_dev reads a plain job's sums: a checked job takes finish_checked_dev + unmask_dev");
     if (has_mask && !mc->core.begun) return fail(SDA_ERR_STATE, "unmask before the mask combiner's begin");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
     if (uc.rust_signed || r->job_acc.rust_signed || (has_mask && mc->core.acc.rust_signed))

@@ -1254,6 +1254,138 @@ __global__ __launch_bounds__(kThreads) void unmask_finish_kernel(const uint64_t*
     }
 }
 
+// The finish of a CHECKED reconstruction job (sda_secret_reconstructor_begin_checked_dev): the job's matrix carried `checks`
+// parity columns behind its k secret columns, so batch b owns the k + checks sums lo/hi[b (k + checks) ..]: its k secrets and
+// the syndromes S_d = sum_i u_i x_i^d share_i[b], which are 0 mod p when the rows of the batch lie on one polynomial of degree
+// <= t + k.  One lane = one batch.  It folds the syndromes (N independent folds step through one loop, as above), and on a
+// non-zero one looks for the positions i with S_{d+1} = x_i S_d for every d < checks - 1 (x in Montgomery form: one REDC per
+// test); exactly one = the batch is located, and under SDA_CHECK_CORRECT its secrets lose (R[s][c] / u_c) S_0.  Then the secrets
+// are folded, up to four at a time, corrected and stored compacted; the padding of the last batch is folded and not stored.
+// Everything indexed by a run-time count is consumed where it is produced (the secrets) or lives in an array whose indices are
+// compile-time constants after unrolling (the 16 syndromes): no scratch.
+// The report: counts are reduced over the wave (ballot + popcount) and the workgroup (LDS) before they reach memory, the blame
+// of a position once per wave for all its lanes that name it - a job whose every batch blames one position issues one global
+// atomic per wave for it, not one per batch.  Sums and a minimum: the report does not depend on the order of arrival.
+struct RevealCheckJob {
+    const uint64_t* lo;          // [batches][k + checks]
+    const int64_t* hi;
+    const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
+    const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
+    uint32_t k, checks, n_rows, correct;
+    uint64_t batches, dimension;
+    ModParams mod;
+    uint64_t pinv;
+};
+
+static constexpr int kMaxChecks = 16;                      // SDA_RECONSTRUCT_MAX_CHECKS
+
+// the sums at lo/hi[0 .. N) folded to canonical residues; a lane that is not live folds zeros
+template <int N>
+static __device__ __forceinline__ void fold_group(const uint64_t* __restrict__ lo, const int64_t* __restrict__ hi, bool live,
+                                                  const ModParams& mod, uint64_t (&o)[4]) {
+    FoldState f[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) f[j] = fold_head(live ? lo[j] : 0, live ? hi[j] : 0, mod);
+    for (int bit = 63; bit >= 0; --bit) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) fold_step(f[j], bit, mod.m);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] = fold_tail(f[j], mod.m);
+}
+static __device__ __forceinline__ void fold_up_to_4(uint32_t n, const uint64_t* __restrict__ lo, const int64_t* __restrict__ hi,
+                                                    bool live, const ModParams& mod, uint64_t (&o)[4]) {
+    o[0] = o[1] = o[2] = o[3] = 0;
+    if (n >= 4) fold_group<4>(lo, hi, live, mod, o);       // n is wave-uniform
+    else if (n == 3) fold_group<3>(lo, hi, live, mod, o);
+    else if (n == 2) fold_group<2>(lo, hi, live, mod, o);
+    else fold_group<1>(lo, hi, live, mod, o);
+}
+
+__global__ __launch_bounds__(kThreads) void reveal_check_finish_kernel(RevealCheckJob J, int64_t* __restrict__ out,
+                                                                       unsigned long long* __restrict__ report) {
+    __shared__ unsigned int wg_count[3];                   // bad, located, corrected batches of this workgroup
+    __shared__ unsigned long long wg_first;
+    if (threadIdx.x == 0) {
+        wg_count[0] = wg_count[1] = wg_count[2] = 0;
+        wg_first = ~0ull;
+    }
+    __syncthreads();
+    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = b < J.batches;
+    const int lane = threadIdx.x & 63;
+    const uint32_t width = J.k + J.checks;
+    const uint64_t* lo = J.lo + (live ? b : 0) * width;
+    const int64_t* hi = J.hi + (live ? b : 0) * width;
+    const uint64_t m = J.mod.m;
+
+    uint64_t S[kMaxChecks];
+#pragma unroll
+    for (int g = 0; g < kMaxChecks / 4; ++g) {
+        uint64_t o[4] = {0, 0, 0, 0};
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
+    }
+    uint64_t any = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
+    const bool bad = live && any != 0;
+
+    uint32_t where = 0, fits = 0;
+    if (bad && J.checks >= 2 && S[0] != 0) {
+        for (uint32_t i = 0; i < J.n_rows; ++i) {
+            const uint64_t x = J.xs[i];
+            bool fit = true;
+#pragma unroll
+            for (int d = 0; d + 1 < kMaxChecks; ++d)
+                if ((uint32_t)(d + 1) < J.checks) fit = fit && mont_redc(mul64x64(x, S[d]), m, J.pinv) == S[d + 1];
+            if (fit) { where = i; ++fits; }
+        }
+    }
+    const bool located = fits == 1;
+    const bool fix = located && J.correct != 0;
+
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t e = b * J.k + s0 + j;
+            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
+            uint64_t v = o[j];
+            if (fix) v = submod(v, mont_redc(mul64x64(J.corr[(uint64_t)(s0 + j) * J.n_rows + where], S[0]), m, J.pinv), m);
+            out[e] = (int64_t)v;
+        }
+    }
+
+    // ---- the report ----
+    const unsigned long long bad_lanes = __ballot(bad), located_lanes = __ballot(located), fixed_lanes = __ballot(fix);
+    if (lane == 0 && bad_lanes != 0) {
+        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
+        if (located_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(located_lanes));
+        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
+        atomicMin(&wg_first, (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+    }
+    unsigned long long pending = located_lanes;
+    while (pending) {                                      // one atomic per distinct blamed position of the wave
+        const int leader = __ffsll((long long)pending) - 1;
+        const uint32_t pos = (uint32_t)__shfl((int)where, leader);
+        const unsigned long long same = __ballot(located && where == pos);
+        if (lane == leader) atomicAdd(&report[4 + pos], (unsigned long long)__popcll(same));
+        pending &= ~same;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
+        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
+        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
+        atomicMin(&report[3], wg_first);
+    }
+}
+
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
 // =================================================================================================
@@ -2370,6 +2502,18 @@ hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_rec
     unmask_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_recon_lo, d_recon_hi, recon_mod, d_mask_lo, d_mask_hi,
                                                                            has_mask ? mask_mod : recon_mod, has_mask, len, d_gate_a,
                                                                            d_gate_b, d_out, aligned16(d_out));
+    return hipGetLastError();
+}
+
+hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                      uint32_t k, uint32_t checks, uint32_t n_rows, bool correct, size_t batches, size_t dimension,
+                                      const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
+    if (batches == 0) return hipSuccess;
+    if (checks == 0 || checks > (uint32_t)kMaxChecks) return hipErrorInvalidValue;
+    const uint64_t blocks = ceil_div(batches, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    const RevealCheckJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, batches, dimension, mod, mont.pinv};
+    reveal_check_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
     return hipGetLastError();
 }
 

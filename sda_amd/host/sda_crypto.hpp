@@ -384,6 +384,42 @@ struct SecretReconstructor {
     void finish_dev(int64_t* d_out, size_t out_cap, void* stream = nullptr) {
         detail::check(sda_secret_reconstructor_finish_dev(h, d_out, out_cap, stream));
     }
+    // the checked job (PackedShamir): `checks` parity columns ride behind the k secret columns, the updates above feed it, and the
+    // finish reports which positions disagree with the others (sda_hip.h: the report words, the Reed-Solomon limits)
+    struct RevealCheck {
+        uint64_t bad = 0, located = 0, corrected = 0, first_bad = ~0ull;     // first_bad: 2^64 - 1 = none
+        std::vector<uint64_t> blame;                                          // per position of the index set
+        bool clean() const { return bad == 0; }
+    };
+    void begin_checked_dev(const std::vector<size_t>& indices, size_t n_rows, size_t row_len, unsigned checks, void* stream = nullptr) {
+        if (indices.size() != n_rows) detail::check(SDA_ERR_INVALID_ARGUMENT);
+        detail::check(sda_secret_reconstructor_begin_checked_dev(h, indices.empty() ? nullptr : indices.data(), n_rows, row_len, checks, stream));
+    }
+    // d_report: sda_reconstruct_report_words(n_rows) device words; nothing synchronises or reaches the host
+    void finish_checked_dev(int64_t* d_out, size_t out_cap, uint64_t* d_report, bool correct = false, void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_finish_checked_dev(h, correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, d_out, out_cap, d_report,
+                                                                  stream));
+    }
+    std::pair<std::vector<Secret>, RevealCheck> reconstruct_checked(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares,
+                                                                    unsigned checks, bool correct = false) const {
+        const size_t n = indexed_shares.size();
+        std::vector<size_t> idx(n), lens(n);
+        std::vector<const int64_t*> ptrs(n);
+        for (size_t i = 0; i < n; ++i) {
+            idx[i] = indexed_shares[i].first; ptrs[i] = indexed_shares[i].second.data(); lens[i] = indexed_shares[i].second.size();
+        }
+        std::vector<Secret> out(dimension ? dimension : 1);
+        std::vector<uint64_t> words(sda_reconstruct_report_words(n));
+        size_t n_out = 0;
+        detail::check(sda_secret_reconstructor_reconstruct_checked(h, idx.data(), ptrs.data(), lens.data(), n, checks,
+                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, out.data(), dimension,
+                                                                   &n_out, words.data()));
+        out.resize(n_out);
+        RevealCheck c;
+        c.bad = words[0]; c.located = words[1]; c.corrected = words[2]; c.first_bad = words[3];
+        c.blame.assign(words.begin() + 4, words.end());
+        return {std::move(out), std::move(c)};
+    }
 };
 
 // ---- masking traits -----------------------------------------------------------------------------

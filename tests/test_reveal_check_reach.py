@@ -1,0 +1,122 @@
+"""The model of the checked reveal finish (tests/reveal_check_cases.py) against the C oracle, and what its cases reach - no device.
+tests/test_reveal_check_gpu.py compares the device bit for bit against this model, so the model is proven here first: on clean rows
+it is the oracle's reconstruction, on one faulty position its correction is the oracle's reconstruction of the other rows, and
+every fault planted in the model itself is noticed by at least one case."""
+import numpy as np
+import pytest
+
+import reveal_check_cases as vc
+
+
+def _oracle(case, rows, keep=None):
+    from oracle import coracle
+    p, k, t, n, w2, w3 = vc.SCHEMES[case.scheme]
+    keep = list(range(len(case.indices))) if keep is None else list(keep)
+    canon = (rows[keep][:, :vc.batches(case)].astype(object) % p).astype(np.int64)
+    return coracle.packed_reconstruct(p, k, t, w2, w3, case.dim, [case.indices[i] for i in keep], canon)
+
+
+def _all_verdicts(case, fin):
+    return set(fin.verdicts)
+
+
+@pytest.mark.parametrize("name", [c.name for c in vc.CASES])
+def test_model_equals_the_oracle(name):
+    case, b = vc.BY_NAME[name], vc.build(name)
+    rep, cor = vc.model_finish(case, b.rows, vc.REPORT), vc.model_finish(case, b.rows, vc.CORRECT)
+    # SDA_CHECK_REPORT is the plain reconstruction of the rows as they are
+    assert np.array_equal(rep.out, _oracle(case, b.rows))
+    assert rep.report[:2] == cor.report[:2] and rep.report[3:] == cor.report[3:] and rep.report[2] == 0
+    assert cor.report[2] == cor.report[1] == sum(cor.report[4:])
+    assert np.array_equal(_oracle(case, b.clean_rows), b.want)
+    if case.expect == "clean":
+        assert rep.report == [0, 0, 0, vc.NONE64] + [0] * len(case.indices), rep.report[:4]
+        assert np.array_equal(rep.out, b.want) and np.array_equal(cor.out, b.want)
+    elif case.expect == "located":
+        assert rep.report[0] > 0 and rep.report[1] == rep.report[0]
+        assert {i for i, n in enumerate(rep.report[4:]) if n} == set(b.faulty)
+        assert np.array_equal(cor.out, b.want), "a batch with one faulty position is corrected to the true secrets"
+        assert not np.array_equal(rep.out, b.want)
+    elif case.expect == "unlocated":
+        assert rep.report[0] > 0 and rep.report[1] == 0 and not any(rep.report[4:])
+        assert np.array_equal(cor.out, rep.out)
+    if b.faulty is not None and len(b.faulty) == 1 and case.checks >= 2:
+        keep = [i for i in range(len(case.indices)) if i != b.faulty[0]]
+        assert np.array_equal(cor.out, _oracle(case, b.rows, keep)), "the correction is the reconstruction of the other rows"
+        assert np.array_equal(cor.out, vc.unchecked_python(case, b.rows, keep))
+
+
+def test_cases_reach_every_verdict():
+    reached = set()
+    for case in vc.CASES:
+        b = vc.build(case.name)
+        fin = vc.model_finish(case, b.rows, vc.CORRECT)
+        B = vc.batches(case)
+        v = set(fin.verdicts)
+        if v == {"clean"}:
+            reached.add("clean")
+        if "located" in v:
+            reached.add("bad + located")
+            if fin.report[2]:
+                reached.add("corrected")
+        if "unlocated" in v:
+            reached.add("bad + unlocated")
+        padded = case.dim % vc.SCHEMES[case.scheme][1] != 0
+        if case.fault == "last" and padded and B > 1 and fin.verdicts[:-1] == ["clean"] * (B - 1) and fin.verdicts[-1] != "clean":
+            assert fin.report[3] == B - 1
+            reached.add("last-batch-only")
+        if case.fault == "surplus" and v == {"clean"} and not np.array_equal(b.rows, b.clean_rows):
+            reached.add("surplus-ignored")
+        if case.values == "congruent" and v == {"clean"} and not (b.rows == b.clean_rows).any():
+            reached.add("congruent-but-different")
+        reached.add("path " + vc.coef_path(case))
+        if len({i for i, n in enumerate(fin.report[4:]) if n}) >= 2 and case.fault == "disjoint":
+            reached.add("two positions blamed")
+    assert reached == {"clean", "bad + located", "bad + unlocated", "corrected", "last-batch-only", "surplus-ignored",
+                       "congruent-but-different", "path lds", "path global", "two positions blamed"}, reached
+
+
+def test_shapes_sit_where_something_can_break():
+    by = vc.BY_NAME
+    assert {vc.width(c) for c in vc.CASES if c.scheme == "k8_62" and len(c.indices) == 26} == {16, 17}          # either side of kCoefLds
+    assert vc.coef_path(by["k8_62-c8-d805-row"]) == "lds" and vc.coef_path(by["k8_62-c9-d805-row"]) == "global"
+    assert vc.width(by["pss155-c5-d250-row"]) == 105 and vc.redundancy(by["pss155-c5-d250-row"]) == 5
+    assert vc.redundancy(by["k3_62-five-c1-d1000-row"]) == 1 and vc.redundancy(by["k3_31-c1-d1000-row"]) == 1
+    assert vc.redundancy(by["k8_62-twelve-c2-d805-row"]) == 2
+    assert vc.batches(by["k3_62-c4-d1000-row"]) == 334 and 334 * 7 > 2048 and 334 > 256                          # window, workgroups
+    assert {c.dim for c in vc.CASES if c.scheme == "k3_62" and c.indices == vc.ALL8} >= {1, 3, 4, 1000, 6301}
+    assert {c.checks for c in vc.CASES if c.scheme == "k3_62" and c.dim == 6301} == {1, 2, 4}
+    assert all(1 <= c.checks <= min(vc.redundancy(c), vc.MAX_CHECKS) for c in vc.CASES)
+    assert {c.feed for c in vc.CASES} == {"one", "descending"}
+    # the any-int64 rows hold the extremes
+    rows = vc.build("k3_62-c4-d1000-crafted").rows
+    assert vc.I64_MIN in rows and vc.I64_MAX in rows
+
+
+def test_two_faulty_rows_are_located_to_nobody():
+    """with >= 3 syndromes that is the Vandermonde argument; with 2 the seeds are pinned (the case names) and the model is asked"""
+    seen = set()
+    for case in vc.CASES:
+        if case.fault != "two":
+            continue
+        fin = vc.model_finish(case, vc.build(case.name).rows, vc.CORRECT)
+        assert fin.report[0] == vc.batches(case) and fin.report[1] == 0, case.name
+        seen.add(min(case.checks, 3))
+    assert seen == {1, 2, 3}
+
+
+PLANTS = ("weight", "no_node1", "locate", "sign")
+
+
+@pytest.mark.parametrize("plant", PLANTS)
+def test_a_planted_model_fault_is_noticed(plant):
+    """a wrong syndrome weight, node 1 dropped from u_i, the locate loop one short, the correction's sign: some case differs"""
+    probes = ["k3_62-c4-d4-clean", "k3_62-c4-d4-row", "k3_62-c2-d4-last", "k3_62-c3-d1000-two", "k8_62-twelve-c2-d805-row"]
+    noticed = []
+    for name in probes:
+        case, b = vc.BY_NAME[name], vc.build(name)
+        good, off = vc.model_finish(case, b.rows, vc.CORRECT), vc.model_finish(case, b.rows, vc.CORRECT, plant=plant)
+        if good.report != off.report or not np.array_equal(good.out, off.out):
+            noticed.append(name)
+    print(plant, "noticed by", noticed)
+    assert noticed, plant
