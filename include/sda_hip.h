@@ -724,7 +724,9 @@ int sda_job_container_get_row(const uint8_t* buf, size_t n_bytes, size_t row, co
  *           4, foreign character, misplaced '=', stray bits under the padding: "Base64 decoding error",
  *           helpers.rs:183) ORs 8 into *d_status and sets d_row_status[r] (optional, zero it beforehand).  A row whose
  *           d_text_bytes[r] exceeds max_chars is malformed as well (the lengths are network input): d_out_bytes[r] = 0,
- *           the same status bits, and not one byte of it is read or written.
+ *           the same status bits, and not one byte of it is read or written.  What a malformed row leaves behind - its
+ *           bytes and d_out_bytes[r] - is unspecified, but stays within the first sda_base64_decoded_max(d_text_bytes[r])
+ *           bytes of its slot: callers go by d_row_status (or *d_status), never by the bytes.
  *   encode: raw row r at d_in + r * in_slot (4-byte aligned rows) -> text row at d_text + r * text_slot (16-byte
  *           aligned rows, text_slot >= sda_base64_encoded_size(max_bytes)), its length to d_text_bytes[r].  A row
  *           with d_in_bytes[r] > max_bytes is refused: d_text_bytes[r] = 0, nothing read or written. */

@@ -43,7 +43,7 @@ def test_base64_rows_roundtrip_vs_oracle(gpu, lens):
         assert got_len[r] == len(texts[r])
         assert tb[r * text_slot:r * text_slot + len(texts[r])] == texts[r], f"row {r}"
     # and back
-    d_out = DeviceBytes(rows * in_slot).zero()
+    d_out = DeviceBytes.from_bytes(b"\xA5" * (rows * in_slot))            # not zeros: a stray zero byte past a row has to show
     d_out_bytes = DeviceBytes(rows * 8).zero()
     d_status = DeviceBytes(4).zero()
     d_rs = DeviceBytes(rows * 4).zero()
@@ -54,7 +54,7 @@ def test_base64_rows_roundtrip_vs_oracle(gpu, lens):
     assert list(_u64(d_out_bytes, rows)) == lens
     for r in range(rows):
         assert ob[r * in_slot:r * in_slot + lens[r]] == raws[r], f"row {r}"
-        assert ob[r * in_slot + lens[r]:(r + 1) * in_slot] == bytes(in_slot - lens[r])        # nothing written past a row
+        assert ob[r * in_slot + lens[r]:(r + 1) * in_slot] == b"\xA5" * (in_slot - lens[r])   # nothing written past a row
 
 
 def test_base64_more_rows_than_one_launch_slice(gpu):
