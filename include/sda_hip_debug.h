@@ -112,6 +112,14 @@ int  sda_debug_secret_masker_mask_sealed_rows_seeded_dev(struct sda_secret_maske
  * the plan head; the driver itself never waits, in either library.  The handle that made the call must still be alive.
  * SDA_ERR_STATE before the first expansion. */
 int  sda_debug_last_mask_plan(unsigned out[4]);
+/* The schedule fuse_plan (sda_kernels.hip) made for the last dual-role launch it was asked for on this thread - the additive, limb-31,
+ * 62-bit limb GEMM and narrow one-limb forms of sda_share_generator_generate_combine_dev; the narrow limb GEMM plans on its own -
+ * out = { fused, n_gen, n_comb, period, grid, splits, rows_per_split, col_blocks }: share-gen chunks and clerk-sum items of the grid,
+ * the distance between two clerk-sum positions, the workgroups launched, the row splits of the previous tile with their row count,
+ * the column blocks.  fused = 0: the plan was refused (the grid too large, a layout the 16-byte accesses do not admit) and the call
+ * went through two launches; the other fields are still what was computed.  Host values only: the query does not wait for the
+ * device.  SDA_ERR_STATE before the first plan.  For tests/test_dual_role_schedule_gpu.py. */
+int  sda_debug_last_fuse_plan(unsigned long long out[8]);
 struct sda_sharing_scheme;
 int  sda_debug_select_path(const struct sda_sharing_scheme* scheme, const char* knobs, char* out, size_t cap);
 #ifdef __cplusplus

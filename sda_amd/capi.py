@@ -265,6 +265,7 @@ HOOK_SIGNATURES = {
                                                                       C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p,
                                                                       C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_debug_last_mask_plan": (C.c_int, [C.POINTER(C.c_uint * 4)]),
+    "sda_debug_last_fuse_plan": (C.c_int, [C.POINTER(C.c_ulonglong * 8)]),
 }
 
 _loaded = {}          # path -> CDLL with signatures attached

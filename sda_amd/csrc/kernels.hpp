@@ -63,6 +63,10 @@ void note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // keeps reporting the last share-generation call whatever reveals follow it.  The grouped kernel is named with its partition:
 // "packed_reconstruct_kernel groups=9 e_per_group=2".
 void note_reveal_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// What fuse_plan (sda_kernels.hip) decided for the dual-role launch it was last asked for on this thread, refused plans included:
+// { fused, n_gen, n_comb, period, grid, splits, rows_per_split, col_blocks }.  Kept by the test library only
+// (sda_debug_last_fuse_plan, for tests/test_dual_role_schedule_gpu.py); the release library's note_fuse_plan does nothing.
+void note_fuse_plan(const unsigned long long plan[8]);
 
 // strides in elements
 struct GenLayout {

@@ -188,6 +188,23 @@ void sda::note_reveal_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 #ifdef SDA_TEST_HOOKS
+// the last plan fuse_plan made on this thread (host values only: nothing here touches the device)
+static thread_local unsigned long long g_last_fuse_plan[8];
+static thread_local bool g_have_fuse_plan = false;
+void sda::note_fuse_plan(const unsigned long long plan[8]) {
+    memcpy(g_last_fuse_plan, plan, sizeof g_last_fuse_plan);
+    g_have_fuse_plan = true;
+}
+extern "C" int sda_debug_last_fuse_plan(unsigned long long out[8]) {
+    if (!out) return fail(SDA_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (!g_have_fuse_plan) return fail(SDA_ERR_STATE, "no dual-role launch has been planned on this thread");
+    memcpy(out, g_last_fuse_plan, sizeof g_last_fuse_plan);
+    return SDA_OK;
+}
+#else
+void sda::note_fuse_plan(const unsigned long long*) {}
+#endif
+#ifdef SDA_TEST_HOOKS
 extern "C" const char* sda_debug_last_reveal_kernel(void) { return g_last_reveal_kernel; }
 extern "C" int sda_debug_stream_create(void** stream) {
     if (!stream) return fail(SDA_ERR_INVALID_ARGUMENT, "stream is NULL");

@@ -2323,10 +2323,11 @@ static bool fuse_plan(const GenLayout& L, uint64_t chunks, uint64_t* acc_lo, int
     if (F.n_comb && (F.period & 1) == 0) F.period = F.period > 2 ? F.period - 1 : 3;
     F.grid = F.n_gen + F.n_comb;
     if (F.n_comb && (F.n_comb - 1) * F.period + 1 > F.grid) F.grid = (F.n_comb - 1) * F.period + 1;   // surplus positions idle
-    if (F.grid == 0 || F.grid > kMaxBlocks) return false;
-    if (F.n_gen && !gen_vec_ok(L, 0)) return false;
-    if (have_comb && !(aligned16(d_prev) && (F.job_stride % 2 == 0) && (F.row_stride % 2 == 0))) return false;
-    return true;
+    const bool fused = F.grid != 0 && F.grid <= kMaxBlocks && (!F.n_gen || gen_vec_ok(L, 0)) &&
+                       (!have_comb || (aligned16(d_prev) && (F.job_stride % 2 == 0) && (F.row_stride % 2 == 0)));
+    const unsigned long long plan[8] = {fused, F.n_gen, F.n_comb, F.period, F.grid, F.splits, F.rows_per_split, F.col_blocks};
+    note_fuse_plan(plan);                                           // host only: sda_debug_last_fuse_plan (test library)
+    return fused;
 }
 
 template <int K, int T, int ROUNDS>
