@@ -470,6 +470,50 @@ int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, 
                                                  unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
                                                  uint64_t* report /* host, sda_reconstruct_report_words(n_rows) */);
 
+/* The DECODING finish of a checked job: the same syndromes correct up to floor(checks / 2) faulty rows per batch, not one.  With
+ * errors e_i on a set E of positions, S_d = sum_{i in E} Y_i * x_i^d with Y_i = u_i * e_i: power sums, a Reed-Solomon decoding
+ * problem.  With a cap e <= floor(checks / 2), a batch is DECODED WITH nu POSITIONS (1 <= nu <= e) when nu distinct positions of
+ * the job and non-zero Y exist that reproduce ALL `checks` syndromes; because 2 e <= checks and the x_i are distinct that
+ * solution is unique when it exists (Vandermonde), so the verdict is a property of the syndromes, not of the algorithm.  The
+ * kernel finds it with inversion-free Berlekamp-Massey, a root search over the job's points and one Fermat inversion per position;
+ * for nu == 1 the verdict is finish_checked_dev's LOCATED.
+ *
+ *   finish_decoded_dev : runs on a job begun by begin_checked_dev and fed like any; it is another way to END such a job, so
+ *               everything upstream (begin_checked_dev, the updates, the tables) is shared with finish_checked_dev.
+ *               max_errors == 0 means floor(checks / 2).  A plain job (begin_dev), no job, or an unfed position -> SDA_ERR_STATE;
+ *               max_errors > floor(checks / 2), a job with checks < 2, a policy other than the two, a NULL d_out / d_report or
+ *               out_cap < dimension -> SDA_ERR_INVALID_ARGUMENT.  Every refusal comes before any launch and leaves the job as it
+ *               was.  Everything is enqueued on the stream: NO SYNCHRONISATION AND NO COPY TO THE HOST.  One kernel.  Ends the job.
+ *                 SDA_CHECK_REPORT : d_out[0 .. dimension) is bit for bit finish_dev's for the same rows; the report still says
+ *                                    what would be decoded ([2] stays 0).
+ *                 SDA_CHECK_CORRECT: a decoded batch's k secrets lose sum_j (R[s][i_j] / u_{i_j}) * Y_j - when at most e rows of
+ *                                    the batch are truly faulty, bit for bit what sda_secret_reconstructor_reconstruct returns
+ *                                    for the other n_rows - nu rows; every other batch as under SDA_CHECK_REPORT.
+ *               d_report (device, sda_reconstruct_decode_report_words(n_rows) = 16 + n_rows words, initialised by the call):
+ *               [0] bad batches, [1] decoded batches, [2] corrected batches, [3] the first bad batch, [4] the first UNDECODED
+ *               batch (2^64 - 1: none, for both), [5] the largest nu decoded, [6], [7] zero, [8 + nu - 1] batches decoded with
+ *               exactly nu positions (nu = 1 .. 8), [16 + i] batches that blame POSITION i (the position in `indices`); a batch
+ *               blames each of its nu positions once.  Sums, minima and one maximum: the report is deterministic.
+ *   reconstruct_decoded : the host form - reconstruct_checked with max_errors after checks and the larger report (host,
+ *               16 + n_rows words); checks < 2 or max_errors > floor(checks / 2) -> SDA_ERR_INVALID_ARGUMENT.
+ *
+ *   What is guaranteed with cap e (Reed-Solomon limits), per batch: 1 .. e faulty rows are decoded and corrected exactly;
+ *   e + 1 .. checks - e faulty rows are always DETECTED and never mis-corrected (they stay undecoded: [4] names the first);
+ *   more than checks - e faulty rows MAY be decoded to wrong positions and mis-corrected, and more than checks may pass
+ *   unnoticed.  A lower cap buys detection margin: max_errors = 1 on 16 checks refuses everything from 2 to 15 faulty rows.
+ *   A clerking result whose box was refused by the sealed update adds nothing to the sums: it is a blamed position here, and up
+ *   to e of them are repaired - which still does NOT replace checking *d_status of the sealed updates: the reference fails the
+ *   whole reveal on such a box (sodium.rs:78-80).  The padding of the last batch is decoded like any batch and not stored
+ *   (batched.rs:94).  Values that differ by a multiple of p are the same share: clean. */
+size_t sda_reconstruct_decode_report_words(size_t n_rows);       /* 16 + n_rows */
+int sda_secret_reconstructor_finish_decoded_dev(sda_secret_reconstructor_t* r, unsigned max_errors, int policy, int64_t* d_out,
+                                                size_t out_cap, uint64_t* d_report, void* stream);
+int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                 const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                 unsigned checks, unsigned max_errors, int policy, int64_t* out, size_t out_cap,
+                                                 size_t* out_len,
+                                                 uint64_t* report /* host, sda_reconstruct_decode_report_words(n_rows) */);
+
 /* =============================================================================================
  * SecretMasker / MaskCombiner / SecretUnmasker  (masking/mod.rs:9-31; impl none.rs, full.rs, chacha.rs)
  * ============================================================================================= */

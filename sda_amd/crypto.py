@@ -426,6 +426,34 @@ class RevealCheck(NamedTuple):
         return cls(w[0], w[1], w[2], None if w[3] == 0xFFFFFFFFFFFFFFFF else w[3], tuple(w[4:]))
 
 
+class RevealDecode(NamedTuple):
+    """the report of a decoded reconstruction: batches with a non-zero syndrome, those decoded (with 1 .. 8 positions), those
+    corrected, the first bad and the first UNDECODED batch (None: none), the largest number of positions a batch was decoded with,
+    by_count[nu - 1] = batches decoded with exactly nu positions and, per POSITION of the index set, the batches that blame it"""
+    bad: int
+    decoded: int
+    corrected: int
+    first_bad: Optional[int]
+    first_undecoded: Optional[int]
+    most: int
+    by_count: Tuple[int, ...]
+    blame: Tuple[int, ...]
+
+    @property
+    def clean(self) -> bool:
+        return self.bad == 0
+
+    @property
+    def undecoded(self) -> int:
+        return self.bad - self.decoded
+
+    @classmethod
+    def from_words(cls, words: Sequence[int]) -> "RevealDecode":
+        w = [int(x) & 0xFFFFFFFFFFFFFFFF for x in words]
+        none = 0xFFFFFFFFFFFFFFFF
+        return cls(w[0], w[1], w[2], None if w[3] == none else w[3], None if w[4] == none else w[4], w[5], tuple(w[8:16]), tuple(w[16:]))
+
+
 class SecretReconstructor(_Handle):
     """sharing/mod.rs:31-33; impl additive.rs:55-73 | batched.rs:68-97 + packed_shamir.rs:73-77."""
     _free = "sda_secret_reconstructor_free"
@@ -535,6 +563,49 @@ class SecretReconstructor(_Handle):
         del held
         _raise_sealed_status(int(back[0]))
         return back[5 + rows:5 + rows + n_out].copy(), RevealCheck.from_words(back[1:5 + rows].view(np.uint64).tolist())
+
+    # the decoding finish of a checked job: up to floor(checks / 2) disagreeing clerking results per batch, named and repaired
+    def finish_decoded_dev(self, d_out: int, out_cap: int, d_report: int, max_errors: int = 0, correct: bool = False,
+                           stream: int = 0) -> None:
+        """ends a job begun by begin_checked_dev: folds, decodes every bad batch with at most max_errors positions (0:
+        floor(checks / 2)), corrects on request; d_report: 16 + n_rows device words (RevealDecode.from_words).  Nothing
+        synchronises or reaches the host"""
+        check(self._lib.sda_secret_reconstructor_finish_decoded_dev(self._h, max_errors, capi.CHECK_CORRECT if correct else capi.CHECK_REPORT,
+                                                                    d_out or None, out_cap, d_report or None, stream or None))
+
+    def reconstruct_decoded(self, indexed_shares: Sequence[Tuple[int, Sequence]], checks: Optional[int] = None, max_errors: int = 0,
+                            correct: bool = False) -> Tuple[np.ndarray, "RevealDecode"]:
+        """reconstruct_checked with the decoding finish: (values, RevealDecode)"""
+        idx = [int(i) for i, _ in indexed_shares]
+        arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
+        cidx = (C.c_size_t * max(len(idx), 1))(*idx)
+        if checks is None and not isinstance(self.scheme, Additive):
+            checks = self.default_checks(len(arrs))
+        out = np.empty(max(self.dimension, 1), dtype=np.int64)
+        report = (C.c_uint64 * (16 + len(arrs)))()
+        n_out = C.c_size_t()
+        check(self._lib.sda_secret_reconstructor_reconstruct_decoded(
+            self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0), max_errors,
+            capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, _ptr(out), self.dimension, C.byref(n_out), report))
+        return out[:n_out.value].copy(), RevealDecode.from_words(list(report))
+
+    def reconstruct_sealed_job_decoded(self, blob, indices: Sequence[int], pk: bytes, sk: bytes, checks: Optional[int] = None,
+                                       max_errors: int = 0, correct: bool = False) -> Tuple[np.ndarray, "RevealDecode"]:
+        """reconstruct_sealed_job_checked with the decoding finish: (values, RevealDecode).  A bad box still fails the reveal
+        (sodium.rs:78-80)"""
+        from .device import DeviceBuffer
+        job = _parse_sealed_job("reconstruct_sealed_job_decoded", blob)
+        row_len, n_out = self._sealed_job_shape(None)
+        rows = job.layout.rows
+        checks = self.default_checks(rows) if checks is None else checks
+        # [0]: the status word, [1 .. 17 + rows): the report, then the output
+        d_buf = DeviceBuffer(1 + 16 + rows + max(n_out, 1)).zero()
+        held = self._feed_sealed_job(job, indices, row_len, pk, sk, d_buf.at(0), checks=checks)
+        self.finish_decoded_dev(d_buf.at(17 + rows), n_out, d_buf.at(1), max_errors, correct)
+        back = d_buf.to_numpy()
+        del held
+        _raise_sealed_status(int(back[0]))
+        return back[17 + rows:17 + rows + n_out].copy(), RevealDecode.from_words(back[1:17 + rows].view(np.uint64).tolist())
 
     def reconstruct_sealed_job(self, blob, indices: Optional[Sequence[int]], pk: bytes, sk: bytes,
                                row_len: Optional[int] = None) -> np.ndarray:
@@ -922,6 +993,22 @@ def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indice
     SecretReconstructor.finish_checked_dev + SecretUnmasker.unmask_dev - the one-kernel unmask_jobs_dev reads a plain job only.
     Returns (RecipientOutput, RevealCheck); correct=True repairs every batch that one clerking result alone spoils.  The failures of
     reveal_sealed stay: a bad box fails the reveal whatever the check says (sodium.rs:78-80)."""
+    return _reveal_sealed_with_checks("reveal_sealed_checked", aggregation, mask_job, result_job, indices, recipient_pk, recipient_sk,
+                                      checks, None, correct)
+
+
+def reveal_sealed_decoded(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
+                          recipient_sk: bytes, checks: Optional[int] = None, max_errors: int = 0, correct: bool = False):
+    """reveal_sealed_checked with SecretReconstructor.finish_decoded_dev in the chain: up to max_errors (0: floor(checks / 2))
+    disagreeing clerking results per batch are named and, with correct=True, repaired.  Returns (RecipientOutput, RevealDecode).
+    A bad box still fails the reveal (sodium.rs:78-80)."""
+    return _reveal_sealed_with_checks("reveal_sealed_decoded", aggregation, mask_job, result_job, indices, recipient_pk, recipient_sk,
+                                      checks, max_errors, correct)
+
+
+def _reveal_sealed_with_checks(name: str, aggregation: Aggregation, mask_job, result_job, indices, recipient_pk: bytes, recipient_sk: bytes,
+                               checks: Optional[int], max_errors: Optional[int], correct: bool):
+    """the chain of reveal_sealed_checked (max_errors None: finish_checked_dev) and reveal_sealed_decoded (finish_decoded_dev)"""
     from .device import DeviceBuffer
     a = aggregation
     sch, msch = a.committee_sharing_scheme, a.masking_scheme
@@ -929,8 +1016,8 @@ def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indice
         raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
     if msch.has_mask() != (mask_job is not None):
         raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
-    masks = _parse_sealed_job("reveal_sealed_checked", mask_job) if mask_job is not None else None
-    results = _parse_sealed_job("reveal_sealed_checked", result_job)
+    masks = _parse_sealed_job(name, mask_job) if mask_job is not None else None
+    results = _parse_sealed_job(name, result_job)
     if isinstance(sch, Additive):
         raise SdaError(capi.ERR_UNSUPPORTED, "additive sharing has no redundancy to check")
     rows = results.layout.rows
@@ -941,24 +1028,29 @@ def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indice
     checks = reconstructor.default_checks(rows) if checks is None else checks
     unmasker = SecretUnmasker(msch)
     combiner = MaskCombiner(msch) if masks is not None else None
-    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 6 + rows): the report, then the masked output, the
+    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the masked output, the
     # combined mask and the output
     cap = max(n_out, 1)
-    d_buf = DeviceBuffer(6 + rows + 3 * cap).zero()
-    d_masked, d_mask, d_out = (d_buf.at(6 + rows + i * cap) for i in range(3))
+    words = (4 if max_errors is None else 16) + rows
+    d_buf = DeviceBuffer(2 + words + 3 * cap).zero()
+    d_masked, d_mask, d_out = (d_buf.at(2 + words + i * cap) for i in range(3))
     held = []
     if combiner is not None:
         held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
         combiner.finish_dev(d_mask, n_out)
     held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks))
-    reconstructor.finish_checked_dev(d_masked, n_out, d_buf.at(2), correct)
+    if max_errors is None:
+        reconstructor.finish_checked_dev(d_masked, n_out, d_buf.at(2), correct)
+    else:
+        reconstructor.finish_decoded_dev(d_masked, n_out, d_buf.at(2), max_errors, correct)
     unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
     back = d_buf.to_numpy()
     del held
     _raise_sealed_status(int(back[0]) | int(back[1]))
-    first = 6 + rows + 2 * cap
+    first = 2 + words + 2 * cap
+    report = back[2:2 + words].view(np.uint64).tolist()
     return (RecipientOutput(a.modulus, back[first:first + n_out].copy()),
-            RevealCheck.from_words(back[2:6 + rows].view(np.uint64).tolist()))
+            RevealCheck.from_words(report) if max_errors is None else RevealDecode.from_words(report))
 
 
 # ---- share-vector wire codec -------------------------------------------------------------

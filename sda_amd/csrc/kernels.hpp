@@ -258,6 +258,15 @@ hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_rec
 hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
                                       uint32_t k, uint32_t checks, uint32_t n_rows, bool correct, size_t batches, size_t dimension,
                                       const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
+// the DECODING finish of the same job: per batch with a non-zero syndrome, Berlekamp-Massey + root search + magnitudes
+// (reveal_decode.hpp); decoded with nu <= max_errors <= checks / 2 positions = all `checks` syndromes are reproduced by nu positions
+// of the job.  Under `correct` the secrets lose sum_j corr[s][i_j] Y_j.  d_report [16 + n_rows], initialised by the caller to 0
+// with [3] = [4] = 2^64 - 1: bad, decoded, corrected batches, first bad, first undecoded batch, largest nu, 0, 0, batches decoded
+// with nu = 1 .. 8, batches that blame position i
+hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                       uint32_t k, uint32_t checks, uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches,
+                                       size_t dimension, const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report,
+                                       hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

@@ -2148,6 +2148,73 @@ extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstru
     return SDA_OK;
 }
 
+// ---- the decoding finish: up to floor(checks / 2) faulty positions per batch, from the same syndromes ---------------------------
+// With errors e_i on a set E the syndromes are the power sums S_d = sum_{i in E} (u_i e_i) x_i^d: a Reed-Solomon decoding problem
+// whose solution with |E| <= checks / 2 is unique.  The kernel solves it per batch (reveal_decode.hpp); the tables are begin_checked_dev's.
+extern "C" size_t sda_reconstruct_decode_report_words(size_t n_rows) { return 16 + n_rows; }
+
+extern "C" int sda_secret_reconstructor_finish_decoded_dev(sda_secret_reconstructor_t* r, unsigned max_errors, int policy, int64_t* d_out,
+                                                           size_t out_cap, uint64_t* d_report, void* stream) {
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
+    if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
+    if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
+    if (r->job_checks < 2) return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
+    if (max_errors > r->job_checks / 2)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
+    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
+    if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    if (!d_report) return fail(SDA_ERR_INVALID_ARGUMENT, "d_report is NULL");
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    HIP_TRY(hipMemsetAsync(d_report, 0, sda_reconstruct_decode_report_words(r->job_rows) * 8, s));
+    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, 16, s));                      // no bad batch, no undecoded batch yet
+    const size_t batches = (r->dimension + r->k - 1) / r->k;
+    HIP_TRY(launch_reveal_decode_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                        r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows,
+                                        max_errors ? max_errors : r->job_checks / 2, policy == SDA_CHECK_CORRECT, batches, r->dimension,
+                                        r->mod, r->mont, d_out, d_report, s));
+    NOTE_CALL_KERNELS("reveal_decode_finish_kernel");
+    r->job_begun = false;
+    r->job_checks = 0;
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                            const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                            unsigned checks, unsigned max_errors, int policy, int64_t* out,
+                                                            size_t out_cap, size_t* out_len, uint64_t* report) {
+    if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_len = 0;
+    if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
+    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
+    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
+    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
+    if (checks < 2 || max_errors > checks / 2)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: decoding takes at least 2 checks and at most checks / 2 positions", checks, max_errors);
+    const size_t batches = (r->dimension + r->k - 1) / r->k;
+    for (size_t i = 0; i < n_rows; ++i)
+        if (row_lens[i] < batches) return fail(SDA_ERR_ASSERTION, "share vector %zu shorter than the number of batches (index out of bounds, batched.rs:84)", i);
+    if (batches > 0 && (!out || out_cap < r->dimension)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(r->ctx.use());
+    const size_t stride = batches + (batches & 1), words = sda_reconstruct_decode_report_words(n_rows);
+    SDA_TRY(r->d_shares.reserve(n_rows * stride * 8));
+    SDA_TRY(r->d_out.reserve(r->dimension * 8));
+    SDA_TRY(r->d_report.reserve(words * 8));
+    for (size_t i = 0; i < n_rows && batches; ++i)
+        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
+    SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
+    SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
+    SDA_TRY(sda_secret_reconstructor_finish_decoded_dev(r, max_errors, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
+    if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    SDA_TRY(r->ctx.sync());
+    *out_len = r->dimension;
+    return SDA_OK;
+}
+
 // =================================================================================================
 // Masking
 // =================================================================================================

@@ -22,6 +22,7 @@
 #include "drbg_quad.hpp"
 #include "kernels.hpp"
 #include "modarith.hpp"
+#include "reveal_decode.hpp"
 #include "sbox_primitives.hpp"
 #include "signed_rem.hpp"
 
@@ -1386,6 +1387,136 @@ __global__ __launch_bounds__(kThreads) void reveal_check_finish_kernel(RevealChe
     }
 }
 
+// The DECODING finish of a checked job (sda_secret_reconstructor_finish_decoded_dev): the same sums, tables and lane = batch as
+// above, and a clean lane does the same work - fold the syndromes, fold the secrets, store.  A lane with a non-zero syndrome
+// decodes (reveal_decode.hpp): Berlekamp-Massey for the connection polynomial and L; L <= cap and exactly L roots of the reversed
+// polynomial among the job's points = the batch is decoded with nu = L positions, whose magnitudes Y_j = u_i e_i follow from the
+// first L syndromes; under SDA_CHECK_CORRECT its secrets lose sum_j corr[s][i_j] Y_j.  Positions and magnitudes (at most 8 per
+// lane, indexed at run time) live in LDS, each lane in its own column: no scratch, no barrier between a lane's store and load.
+// The report ([16 + n_rows], see sda_hip.h) is reduced like the sibling's: ballots and shuffles only where the whole wave goes,
+// counts per workgroup in LDS, the blame of a position once per wave and error slot for all lanes that name it there.
+struct RevealDecodeJob {
+    const uint64_t* lo;          // [batches][k + checks]
+    const int64_t* hi;
+    const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
+    const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
+    uint32_t k, checks, n_rows, correct, cap;
+    uint64_t batches, dimension;
+    ModParams mod;
+    uint64_t pinv;
+};
+
+__global__ __launch_bounds__(kThreads) void reveal_decode_finish_kernel(RevealDecodeJob J, int64_t* __restrict__ out,
+                                                                        unsigned long long* __restrict__ report) {
+    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
+    __shared__ unsigned int wg_most;                       // the largest nu
+    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
+    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
+    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
+    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        wg_most = 0;
+        wg_first[0] = wg_first[1] = ~0ull;
+    }
+    __syncthreads();
+    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = b < J.batches;
+    const int lane = threadIdx.x & 63;
+    const uint32_t width = J.k + J.checks;
+    const uint64_t* lo = J.lo + (live ? b : 0) * width;
+    const int64_t* hi = J.hi + (live ? b : 0) * width;
+    const uint64_t m = J.mod.m;
+
+    uint64_t S[kMaxChecks];
+#pragma unroll
+    for (int g = 0; g < kMaxChecks / 4; ++g) {
+        uint64_t o[4] = {0, 0, 0, 0};
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
+    }
+    uint64_t any = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
+    const bool bad = live && any != 0;
+
+    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
+    if (bad) {
+        uint64_t C[kDecodeErrors + 1];
+        const uint32_t L = decode_bm(S, J.checks, m, J.pinv, C);
+        if (L >= 1 && L <= J.cap &&
+            decode_roots(C, J.cap, J.n_rows, J.xs, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L) {
+            uint64_t Om[kDecodeErrors];
+            decode_omega(S, C, J.cap, m, J.pinv, Om);
+            for (uint32_t j = 0; j < L; ++j)
+                dec_y[j][threadIdx.x] = decode_magnitude(C, Om, L, J.xs[dec_pos[j][threadIdx.x]], m, J.pinv);
+            nu = L;
+        }
+    }
+    const bool decoded = nu != 0;
+    const bool fix = decoded && J.correct != 0;
+
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t e = b * J.k + s0 + j;
+            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
+            uint64_t v = o[j];
+            if (fix) {
+                const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
+                for (uint32_t q = 0; q < nu; ++q)
+                    v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
+            }
+            out[e] = (int64_t)v;
+        }
+    }
+
+    // ---- the report ----
+    const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
+    const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
+    if (lane == 0 && bad_lanes != 0) {
+        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
+        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
+        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
+        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
+    }
+    if (decoded_lanes != 0) {                              // wave-uniform
+        for (uint32_t j = 0; j < J.cap; ++j) {
+            const unsigned long long with = __ballot(nu == j + 1);
+            if (lane == 0 && with != 0) {
+                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
+                atomicMax(&wg_most, j + 1);
+            }
+            const bool has = j < nu;
+            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
+            unsigned long long pending = __ballot(has);
+            while (pending) {                              // one atomic per distinct position the wave blames in slot j
+                const int leader = __ffsll((long long)pending) - 1;
+                const uint32_t pos = (uint32_t)__shfl((int)mine, leader);
+                const unsigned long long same = __ballot(has && mine == pos);
+                if (lane == leader) atomicAdd(&report[16 + pos], (unsigned long long)__popcll(same));
+                pending &= ~same;
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
+        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
+        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
+        atomicMin(&report[3], wg_first[0]);
+        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
+        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
+        for (int j = 0; j < kDecodeErrors; ++j)
+            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
+    }
+}
+
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
 // =================================================================================================
@@ -2515,6 +2646,20 @@ hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d
     if (hipError_t e = grid_check(blocks)) return e;
     const RevealCheckJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, batches, dimension, mod, mont.pinv};
     reveal_check_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
+    return hipGetLastError();
+}
+
+hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                       uint32_t k, uint32_t checks, uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches,
+                                       size_t dimension, const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report,
+                                       hipStream_t s) {
+    if (batches == 0) return hipSuccess;
+    if (checks < 2 || checks > (uint32_t)kMaxChecks || max_errors == 0 || max_errors > checks / 2 || n_rows > 65535)   // dec_pos is 16 bits wide
+        return hipErrorInvalidValue;
+    const uint64_t blocks = ceil_div(batches, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    const RevealDecodeJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, max_errors, batches, dimension, mod, mont.pinv};
+    reveal_decode_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 //
 // Header-only; link against libsda_hip.so.  All arithmetic happens on the GPU behind the C ABI.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -419,6 +420,44 @@ struct SecretReconstructor {
         c.bad = words[0]; c.located = words[1]; c.corrected = words[2]; c.first_bad = words[3];
         c.blame.assign(words.begin() + 4, words.end());
         return {std::move(out), std::move(c)};
+    }
+    // the decoding finish of a checked job: up to max_errors (0: checks / 2) disagreeing positions per batch are named and, on
+    // request, repaired (sda_hip.h: the report words, what a cap guarantees)
+    struct RevealDecode {
+        uint64_t bad = 0, decoded = 0, corrected = 0, first_bad = ~0ull, first_undecoded = ~0ull, most = 0;   // 2^64 - 1 = none
+        std::array<uint64_t, 8> by_count{};                                   // by_count[nu - 1]: batches decoded with nu positions
+        std::vector<uint64_t> blame;                                          // per position of the index set
+        bool clean() const { return bad == 0; }
+        static RevealDecode from_words(const std::vector<uint64_t>& w) {
+            RevealDecode d;
+            d.bad = w[0]; d.decoded = w[1]; d.corrected = w[2]; d.first_bad = w[3]; d.first_undecoded = w[4]; d.most = w[5];
+            for (size_t i = 0; i < 8; ++i) d.by_count[i] = w[8 + i];
+            d.blame.assign(w.begin() + 16, w.end());
+            return d;
+        }
+    };
+    // d_report: sda_reconstruct_decode_report_words(n_rows) device words; nothing synchronises or reaches the host
+    void finish_decoded_dev(int64_t* d_out, size_t out_cap, uint64_t* d_report, unsigned max_errors = 0, bool correct = false,
+                            void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_finish_decoded_dev(h, max_errors, correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, d_out, out_cap,
+                                                                  d_report, stream));
+    }
+    std::pair<std::vector<Secret>, RevealDecode> reconstruct_decoded(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares,
+                                                                     unsigned checks, unsigned max_errors = 0, bool correct = false) const {
+        const size_t n = indexed_shares.size();
+        std::vector<size_t> idx(n), lens(n);
+        std::vector<const int64_t*> ptrs(n);
+        for (size_t i = 0; i < n; ++i) {
+            idx[i] = indexed_shares[i].first; ptrs[i] = indexed_shares[i].second.data(); lens[i] = indexed_shares[i].second.size();
+        }
+        std::vector<Secret> out(dimension ? dimension : 1);
+        std::vector<uint64_t> words(sda_reconstruct_decode_report_words(n));
+        size_t n_out = 0;
+        detail::check(sda_secret_reconstructor_reconstruct_decoded(h, idx.data(), ptrs.data(), lens.data(), n, checks, max_errors,
+                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, out.data(), dimension,
+                                                                   &n_out, words.data()));
+        out.resize(n_out);
+        return {std::move(out), RevealDecode::from_words(words)};
     }
 };
 
