@@ -28,6 +28,7 @@
 #include "capi_internal.hpp"
 #include "drbg_lane.hpp"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 #include "modarith.hpp"
 
 namespace sda {
@@ -448,11 +449,6 @@ static hipError_t fft_launch_v(const GenLayout& L, const ModParams& mod, const D
     const long want_threads = F.want_threads;                                   // A/B only (knob SDA_FFT_THREADS when the handle was created)
     unsigned threads = (F.G == 1 && F.m3 > 2187) ? 1024u : 512u;
     if (want_threads >= 64 && want_threads <= 1024 && want_threads % 64 == 0) threads = (unsigned)want_threads;
-    if (rounds != 20 && rounds != 12 && rounds != 8) return hipErrorInvalidValue;
-    auto kern = F.tw_lds ? (rounds == 20 ? packed_gen_fft_kernel<20, true, V, LAZY> : rounds == 12 ? packed_gen_fft_kernel<12, true, V, LAZY> : packed_gen_fft_kernel<8, true, V, LAZY>)
-                         : (rounds == 20 ? packed_gen_fft_kernel<20, false, V, LAZY> : rounds == 12 ? packed_gen_fft_kernel<12, false, V, LAZY> : packed_gen_fft_kernel<8, false, V, LAZY>);
-    if (lds > 64 * 1024)
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
     FftPlan Fl = F;
     Fl.groups_padded = 0;
     uint64_t gridg = groups;
@@ -461,24 +457,20 @@ static hipError_t fft_launch_v(const GenLayout& L, const ModParams& mod, const D
         gridg = (groups + unit - 1) / unit * unit;
         Fl.groups_padded = gridg;
     }
-    const uint64_t max_blocks = 0x7FFFFFFFull;
-    uint64_t per = max_blocks / gridg;
-    if (per == 0) return hipErrorInvalidConfiguration;
-    if (per > L.participants) per = L.participants;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        GenLayout S = L;
-        const uint64_t cnt = per < L.participants - p0 ? per : L.participants - p0;
-        S.secrets = L.secrets + p0 * L.secrets_stride;
-        if (L.rand) S.rand = L.rand + p0 * L.rand_stride;
-        S.out = L.out + p0 * L.out_stride_participant;
-        S.participants = cnt;
-        S.first_participant = L.first_participant + p0;
-        note_kernel("packed_gen_fft_kernel<%d, %s, %s, %s>", rounds, F.tw_lds ? "true" : "false", sizeof(V) == 4 ? "unsigned int" : "unsigned long",
-                    LAZY ? "true" : "false");
-        kern<<<dim3((unsigned)(gridg * cnt)), dim3(threads), lds, s>>>(S, mod, key, Fl, groups, batches);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    auto launch = [&](auto kern) -> hipError_t {
+        if (lds > 64 * 1024)
+            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+        return for_participant_slices(L, gridg, kMaxBlocksI31, [&](const GenLayout& S, uint64_t blocks) {
+            note_kernel("packed_gen_fft_kernel<%d, %s, %s, %s>", rounds, F.tw_lds ? "true" : "false", sizeof(V) == 4 ? "unsigned int" : "unsigned long",
+                        LAZY ? "true" : "false");
+            kern<<<dim3((unsigned)blocks), dim3(threads), lds, s>>>(S, mod, key, Fl, groups, batches);
+            return hipGetLastError();
+        });
+    };
+    return with_rounds(rounds, [&](auto R) {
+        constexpr int ROUNDS = decltype(R)::value;
+        return F.tw_lds ? launch(packed_gen_fft_kernel<ROUNDS, true, V, LAZY>) : launch(packed_gen_fft_kernel<ROUNDS, false, V, LAZY>);
+    });
 }
 
 hipError_t launch_packed_generate_fft(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const FftPlan& F, int rounds,

@@ -82,6 +82,15 @@ struct GenLayout {
     uint32_t direct_rows;
 };
 
+// The clerk-sum side of a dual-role launch (below): the 128-bit column accumulators [jobs][dimension] and the previous tile's
+// shares they take in, prev_rows participants in the SAME layout as the GenLayout's out
+struct ClerkSumTarget {
+    uint64_t* acc_lo;
+    int64_t* acc_hi;
+    const int64_t* prev;
+    size_t prev_rows, jobs, dimension;
+};
+
 // ---- share generation ---------------------------------------------------------------------------
 // additive: k = 1, n shares, n-1 randoms per element (additive.rs:32-51 through batched.rs:18-53)
 hipError_t launch_additive_generate(const GenLayout& L, uint32_t n, const ModParams& mod,
@@ -107,8 +116,7 @@ bool packed_n31_path_available(uint32_t k, uint32_t t, uint32_t rows, uint64_t p
 hipError_t launch_packed_generate_n31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
                                       const N31Params& np, const MatArg& M, const DrbgKey& key, hipStream_t s);
 hipError_t launch_fused_packed_n31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod, const N31Params& np,
-                                   const MatArg& M, const DrbgKey& key, uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev,
-                                   size_t prev_rows, size_t jobs, size_t dimension, hipStream_t s, bool* fused);
+                                   const MatArg& M, const DrbgKey& key, const ClerkSumTarget& C, hipStream_t s, bool* fused);
 
 // packed Shamir as a limb GEMM on the matrix cores (v_mfma_i32_16x16x64_i8 on balanced base-256 digits), compiled shapes
 bool packed_mfma_path_available(uint32_t k, uint32_t t, uint32_t n);
@@ -117,9 +125,8 @@ hipError_t launch_packed_generate_mfma(const GenLayout& L, uint32_t n, uint32_t 
                                        const DrbgKey& key, int rounds, hipStream_t s);
 
 hipError_t launch_fused_packed_mfma(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
-                                    const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, int rounds, uint64_t* acc_lo,
-                                    int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs, size_t dimension,
-                                    hipStream_t s, bool* fused);
+                                    const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, int rounds,
+                                    const ClerkSumTarget& C, hipStream_t s, bool* fused);
 
 // the limb-31 kernel with run-time (k, t) and the matrix in global memory: any n, k + t <= 64
 bool packed_l31_global_path_available(uint32_t k, uint32_t t);
@@ -174,9 +181,9 @@ hipError_t launch_packed_generate_ngemm(const GenLayout& L, const ModParams& mod
 // clerk WAVES of every share-generation workgroup, a follow-up kernel sums what they did not get to (round 6, the default);
 // d_progress == nullptr: clerk WORKGROUPS at fixed positions of the same grid (rounds 4 - 5; A/B knob SDA_NGEMM_CLERK_WG)
 uint64_t ngemm_clerk_slots(const GenLayout& L, const NGemmPlan& P);
-hipError_t launch_fused_packed_ngemm(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const NGemmPlan& P, uint64_t* acc_lo,
-                                     int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs, size_t dimension, hipStream_t s,
-                                     bool* fused, uint64_t* d_progress = nullptr, size_t progress_slots = 0);
+hipError_t launch_fused_packed_ngemm(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const NGemmPlan& P,
+                                     const ClerkSumTarget& C, hipStream_t s, bool* fused, uint64_t* d_progress = nullptr,
+                                     size_t progress_slots = 0);
 
 // packed Shamir, any shape: matrix in global memory, randomness must be materialised (L.rand != 0)
 hipError_t launch_packed_generate_generic(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t,
@@ -212,17 +219,15 @@ hipError_t launch_addsub_signed(const int64_t* d_a, const int64_t* d_b, size_t l
                                 hipStream_t s);
 
 // ---- dual-role launch: share generation of one tile + clerk-sum of the previous tile in ONE grid ----------
-// d_prev holds the previous tile's shares in the SAME layout as L.out (job stride = L.out_stride_clerk, row
-// stride = L.out_stride_participant), prev_rows participants; L.participants may be 0 (clerk-sum only) and
-// d_prev may be null (generation only).  *fused = false (and nothing launched) when the layout or the shape
+// C.prev holds the previous tile's shares in the SAME layout as L.out (job stride = L.out_stride_clerk, row
+// stride = L.out_stride_participant), C.prev_rows participants; L.participants may be 0 (clerk-sum only) and
+// C.prev may be null (generation only).  *fused = false (and nothing launched) when the layout or the shape
 // rules the fused form out - the caller then issues the two ordinary launches.
 hipError_t launch_fused_packed_l31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
-                                   const L31Params& lp, const MatArg& M, const DrbgKey& key, int rounds,
-                                   uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows,
-                                   size_t jobs, size_t dimension, hipStream_t s, bool* fused);
+                                   const L31Params& lp, const MatArg& M, const DrbgKey& key, int rounds, const ClerkSumTarget& C,
+                                   hipStream_t s, bool* fused);
 hipError_t launch_fused_additive(const GenLayout& L, uint32_t n, const ModParams& mod, const DrbgKey& key, int rounds,
-                                 uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows,
-                                 size_t jobs, size_t dimension, hipStream_t s, bool* fused);
+                                 const ClerkSumTarget& C, hipStream_t s, bool* fused);
 
 // ---- packed reconstruct (batched.rs:68-97 + tss reconstruct as a k x n' Lagrange matrix) ------------
 hipError_t launch_packed_reconstruct(const int64_t* d_shares, size_t row_stride, uint32_t n_rows,

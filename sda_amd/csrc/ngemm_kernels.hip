@@ -42,6 +42,7 @@
 #include "clerk_sum.hpp"
 #include "drbg_lane.hpp"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 #include "modarith.hpp"
 
 namespace sda {
@@ -956,24 +957,11 @@ static hipError_t ngemm_launch(const GenLayout& L, const ModParams& mod, const D
     auto kern = packed_gen_ngemm_kernel<KS, NT>;
     if (lds > 64 * 1024)
         if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-    const uint64_t max_blocks = 0x7FFFFFFFull;
-    uint64_t per = max_blocks / chunks;
-    if (per == 0) return hipErrorInvalidConfiguration;
-    if (per > L.participants) per = L.participants;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        GenLayout S = L;
-        const uint64_t cnt = per < L.participants - p0 ? per : L.participants - p0;
-        S.secrets = L.secrets + p0 * L.secrets_stride;
-        if (L.rand) S.rand = L.rand + p0 * L.rand_stride;
-        S.out = L.out + p0 * L.out_stride_participant;
-        S.participants = cnt;
-        S.first_participant = L.first_participant + p0;
+    return for_participant_slices(L, chunks, kMaxBlocksI31, [&](const GenLayout& S, uint64_t blocks) {
         note_kernel("packed_gen_ngemm_kernel<%d, %d>", KS, NT);
-        NgFuse F{};
-        kern<<<dim3((unsigned)(chunks * cnt)), dim3(kNgThreads), lds, s>>>(S, mod, key, P, chunks, batches, F);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+        kern<<<dim3((unsigned)blocks), dim3(kNgThreads), lds, s>>>(S, mod, key, P, chunks, batches, NgFuse{});
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_packed_generate_ngemm(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const NGemmPlan& P, hipStream_t s) {
@@ -1068,25 +1056,24 @@ uint64_t ngemm_clerk_slots(const GenLayout& L, const NGemmPlan& P) {
     return (batches + wgb - 1) / wgb * L.participants * (uint64_t)kNgClerkWaves;
 }
 
-hipError_t launch_fused_packed_ngemm(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const NGemmPlan& P, uint64_t* acc_lo,
-                                     int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs, size_t dimension, hipStream_t s,
-                                     bool* fused, uint64_t* d_progress, size_t progress_slots) {
+hipError_t launch_fused_packed_ngemm(const GenLayout& L, const ModParams& mod, const DrbgKey& key, const NGemmPlan& P,
+                                     const ClerkSumTarget& C, hipStream_t s, bool* fused, uint64_t* d_progress, size_t progress_slots) {
     *fused = false;
     if (L.rand) return hipSuccess;
     if (L.participants == 0 || L.len == 0) return hipSuccess;       // nothing to generate: the plain clerk-sum kernel streams at the HBM rate
-    const bool have_comb = d_prev && prev_rows > 0 && jobs > 0 && dimension > 0;
+    const bool have_comb = C.prev && C.prev_rows > 0 && C.jobs > 0 && C.dimension > 0;
     // the clerk role reads the previous tile with 16-byte loads
-    if (have_comb && !(((reinterpret_cast<uintptr_t>(d_prev) & 15u) == 0) && (L.out_stride_clerk % 2 == 0) && (L.out_stride_participant % 2 == 0)))
+    if (have_comb && !(aligned16(C.prev) && (L.out_stride_clerk % 2 == 0) && (L.out_stride_participant % 2 == 0)))
         return hipSuccess;
     NgFuse F{};
-    F.acc_lo = acc_lo; F.acc_hi = acc_hi; F.prev = d_prev;
+    F.acc_lo = C.acc_lo; F.acc_hi = C.acc_hi; F.prev = C.prev;
     F.job_stride = L.out_stride_clerk; F.row_stride = L.out_stride_participant;
-    F.n_rows = prev_rows; F.dimension = dimension; F.jobs = (uint32_t)jobs;
+    F.n_rows = C.prev_rows; F.dimension = C.dimension; F.jobs = (uint32_t)C.jobs;
     switch (P.ks) {
-        case 1: return ngemm_launch_fused<1, 4>(L, mod, key, P, F, prev_rows, s, fused, d_progress, progress_slots);
-        case 2: return ngemm_launch_fused<2, 2>(L, mod, key, P, F, prev_rows, s, fused, d_progress, progress_slots);
-        case 4: return ngemm_launch_fused<4, 2>(L, mod, key, P, F, prev_rows, s, fused, d_progress, progress_slots);
-        case 8: return ngemm_launch_fused<8, 1>(L, mod, key, P, F, prev_rows, s, fused, d_progress, progress_slots);
+        case 1: return ngemm_launch_fused<1, 4>(L, mod, key, P, F, C.prev_rows, s, fused, d_progress, progress_slots);
+        case 2: return ngemm_launch_fused<2, 2>(L, mod, key, P, F, C.prev_rows, s, fused, d_progress, progress_slots);
+        case 4: return ngemm_launch_fused<4, 2>(L, mod, key, P, F, C.prev_rows, s, fused, d_progress, progress_slots);
+        case 8: return ngemm_launch_fused<8, 1>(L, mod, key, P, F, C.prev_rows, s, fused, d_progress, progress_slots);
         default: return hipErrorInvalidValue;
     }
 }

@@ -1565,14 +1565,13 @@ extern "C" int sda_share_generator_generate_combine_dev(sda_share_generator_t* g
     bool fused = false;
     hipError_t he = hipSuccess;
     g_last_gen_kernel[0] = 0;
+    const ClerkSumTarget sums{c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_prev, prev_participants, c->jobs, c->dimension};
     if (g->additive) {
-        he = launch_fused_additive(L, g->n, g->mod, key, g->drbg.rounds, c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(),
-                                   d_prev, prev_participants, c->jobs, c->dimension, s, &fused);
+        he = launch_fused_additive(L, g->n, g->mod, key, g->drbg.rounds, sums, s, &fused);
     } else switch (fused_for_call(g->path, g->drbg.rounds)) {
         case FAM_N31:
-            he = launch_fused_packed_n31(L, g->n, g->k, g->t, g->mod, g->n31p, sys ? *g->matarg_n31_sys : *g->matarg_n31, key,
-                                         c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_prev, prev_participants, c->jobs, c->dimension,
-                                         s, &fused);
+            he = launch_fused_packed_n31(L, g->n, g->k, g->t, g->mod, g->n31p, sys ? *g->matarg_n31_sys : *g->matarg_n31, key, sums, s,
+                                         &fused);
             break;
         case FAM_NGEMM:
         {
@@ -1583,20 +1582,17 @@ extern "C" int sda_share_generator_generate_combine_dev(sda_share_generator_t* g
                 const int rs = g->d_cw_progress.reserve((size_t)slots * 16);
                 if (rs != SDA_OK) { explicit_bzero(&key, sizeof key); return rs; }
             }
-            he = launch_fused_packed_ngemm(L, g->mod, key, gp, c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_prev,
-                                           prev_participants, c->jobs, c->dimension, s, &fused,
+            he = launch_fused_packed_ngemm(L, g->mod, key, gp, sums, s, &fused,
                                            slots && slots <= (1ull << 32) ? g->d_cw_progress.as<uint64_t>() : nullptr, (size_t)slots);
             break;
         }
         case FAM_L31:
             he = launch_fused_packed_l31(L, g->n, g->k, g->t, g->mod, g->lp, sys ? *g->matarg_sys : *g->matarg, key, g->drbg.rounds,
-                                         c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_prev, prev_participants, c->jobs,
-                                         c->dimension, s, &fused);
+                                         sums, s, &fused);
             break;
         case FAM_MFMA:
             he = launch_fused_packed_mfma(L, g->n, g->k, g->t, g->mod, g->mont, (sys ? g->d_Msys : g->d_M).as<uint64_t>(), key, g->drbg.rounds,
-                                          c->acc.lo.as<uint64_t>(), c->acc.hi.as<int64_t>(), d_prev, prev_participants, c->jobs,
-                                          c->dimension, s, &fused);
+                                          sums, s, &fused);
             break;
         default: break;                                                       // no dual-role kernel for this family
     }

@@ -21,6 +21,7 @@
 #include "clerk_sum.hpp"
 #include "drbg_quad.hpp"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 #include "modarith.hpp"
 #include "reveal_decode.hpp"
 #include "sbox_primitives.hpp"
@@ -2019,81 +2020,47 @@ __global__ __launch_bounds__(kThreads) void modsum_parts_kernel(const int64_t* _
 // =================================================================================================
 // launchers
 // =================================================================================================
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-// HIP limits a launch to < 2^32 work-items per grid dimension
-static constexpr uint64_t kMaxBlocks = (0xFFFFFFFFull / kThreads);
+// the slice loop, the grid limit and the round-count dispatch: launch_plan.hpp
+static_assert(kMaxBlocks == 0xFFFFFFFFull / kThreads, "launch_plan.hpp states the limit for this file's workgroup size");
 static inline hipError_t grid_check(uint64_t blocks) {
     return blocks > kMaxBlocks ? hipErrorInvalidConfiguration : hipSuccess;
 }
-// (participant, chunk)-indexed kernels are launched in slices of participants that respect the limit
-static inline uint64_t participants_per_launch(uint64_t chunks, uint64_t participants) {
-    if (chunks == 0 || chunks > kMaxBlocks) return 0;
-    const uint64_t m = kMaxBlocks / chunks;
-    return m < participants ? m : participants;
-}
-static inline GenLayout slice(const GenLayout& L, uint64_t p0, uint64_t count) {
-    GenLayout S = L;
-    S.secrets = L.secrets + p0 * L.secrets_stride;
-    if (L.rand) S.rand = L.rand + p0 * L.rand_stride;
-    S.out = L.out + p0 * L.out_stride_participant;
-    S.participants = count;
-    S.first_participant = L.first_participant + p0;
-    return S;
-}
 
-static bool gen_vec_ok(const GenLayout& L, size_t secrets_per_lane_even) {
-    (void)secrets_per_lane_even;
-    return aligned16(L.secrets) && aligned16(L.out) && (L.secrets_stride % 2 == 0) &&
-           (L.out_stride_participant % 2 == 0) && (L.out_stride_clerk % 2 == 0);
+// 16-byte stores of the shares / 16-byte loads of the secrets as well
+static bool out_vec_ok(const GenLayout& L) {
+    return aligned16(L.out) && (L.out_stride_participant % 2 == 0) && (L.out_stride_clerk % 2 == 0);
 }
+static bool gen_vec_ok(const GenLayout& L) { return out_vec_ok(L) && aligned16(L.secrets) && (L.secrets_stride % 2 == 0); }
 
 template <int ROUNDS>
 static hipError_t additive_launch_r(const GenLayout& L, uint32_t n, const ModParams& mod, const DrbgKey& key,
                                     hipStream_t s) {
     const uint64_t chunks = ceil_div(ceil_div(L.len, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    const bool vec = gen_vec_ok(L, 0);
-    note_kernel("additive_gen_kernel<%d, %s>", ROUNDS, vec ? "true" : "false");
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const unsigned blocks = (unsigned)(chunks * S.participants);
-        if (vec) additive_gen_kernel<ROUNDS, true><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, key, chunks);
-        else additive_gen_kernel<ROUNDS, false><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, key, chunks);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    const bool vec = gen_vec_ok(L);
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
+        note_kernel("additive_gen_kernel<%d, %s>", ROUNDS, vec ? "true" : "false");
+        if (vec) additive_gen_kernel<ROUNDS, true><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, key, chunks);
+        else additive_gen_kernel<ROUNDS, false><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, key, chunks);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_additive_generate_signed_drbg(const GenLayout& L, uint32_t n, const ModParams& mod, const DrbgKey& key, int rounds,
                                                 hipStream_t s) {
-    if (L.rand || n < 2 || (rounds != 20 && rounds != 12 && rounds != 8)) return hipErrorInvalidValue;
+    if (L.rand || n < 2) return hipErrorInvalidValue;
     const uint64_t chunks = ceil_div(ceil_div(L.len, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    note_kernel("signed_additive_gen_drbg_kernel<%d>", rounds);
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const dim3 grid((unsigned)(chunks * S.participants)), block(kThreads);
-        if (rounds == 20) signed_additive_gen_drbg_kernel<20><<<grid, block, 0, s>>>(S, n, mod, key, chunks);
-        else if (rounds == 12) signed_additive_gen_drbg_kernel<12><<<grid, block, 0, s>>>(S, n, mod, key, chunks);
-        else signed_additive_gen_drbg_kernel<8><<<grid, block, 0, s>>>(S, n, mod, key, chunks);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return with_rounds(rounds, [&](auto R) {
+        return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
+            note_kernel("signed_additive_gen_drbg_kernel<%d>", rounds);
+            signed_additive_gen_drbg_kernel<decltype(R)::value><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, key, chunks);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_additive_generate(const GenLayout& L, uint32_t n, const ModParams& mod, const DrbgKey& key,
                                     int rounds, hipStream_t s) {
-    switch (rounds) {
-        case 20: return additive_launch_r<20>(L, n, mod, key, s);
-        case 12: return additive_launch_r<12>(L, n, mod, key, s);
-        case 8: return additive_launch_r<8>(L, n, mod, key, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_rounds(rounds, [&](auto R) { return additive_launch_r<decltype(R)::value>(L, n, mod, key, s); });
 }
 
 // compiled (k, t) pairs of the fast packed kernel: the BASELINE shapes and their reference-valid
@@ -2113,19 +2080,13 @@ static hipError_t packed_launch_kt(const GenLayout& L, uint32_t n, const ModPara
                                    const MatArg& M, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, K);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    const bool vec = gen_vec_ok(L, 0);
-    note_kernel("packed_gen_kernel<%d, %d, %d, %s>", K, T, ROUNDS, vec ? "true" : "false");
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const unsigned blocks = (unsigned)(chunks * S.participants);
-        if (vec) packed_gen_kernel<K, T, ROUNDS, true><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, mont, M, key, chunks, batches);
-        else packed_gen_kernel<K, T, ROUNDS, false><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, mont, M, key, chunks, batches);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    const bool vec = gen_vec_ok(L);
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
+        note_kernel("packed_gen_kernel<%d, %d, %d, %s>", K, T, ROUNDS, vec ? "true" : "false");
+        if (vec) packed_gen_kernel<K, T, ROUNDS, true><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, mont, M, key, chunks, batches);
+        else packed_gen_kernel<K, T, ROUNDS, false><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, mont, M, key, chunks, batches);
+        return hipGetLastError();
+    });
 }
 
 template <int ROUNDS>
@@ -2140,12 +2101,7 @@ static hipError_t packed_launch_r(const GenLayout& L, uint32_t n, uint32_t k, ui
 hipError_t launch_packed_generate(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
                                   const MontParams& mont, const MatArg& M, const DrbgKey& key, int rounds,
                                   hipStream_t s) {
-    switch (rounds) {
-        case 20: return packed_launch_r<20>(L, n, k, t, mod, mont, M, key, s);
-        case 12: return packed_launch_r<12>(L, n, k, t, mod, mont, M, key, s);
-        case 8: return packed_launch_r<8>(L, n, k, t, mod, mont, M, key, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_rounds(rounds, [&](auto R) { return packed_launch_r<decltype(R)::value>(L, n, k, t, mod, mont, M, key, s); });
 }
 
 // every split of k + t = 7 (the tss-valid family for n = 8: k + t + 1 = 2^3), the BASELINE shapes, small shapes and a
@@ -2183,19 +2139,13 @@ static hipError_t packed_l31_launch_kt(const GenLayout& L, uint32_t n, const Mod
                                        const MatArg& M, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, K);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    const bool vec = gen_vec_ok(L, 0);
-    note_kernel("packed_gen_l31_kernel<%d, %d, %d, %s>", K, T, ROUNDS, vec ? "true" : "false");
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const unsigned blocks = (unsigned)(chunks * S.participants);
-        if (vec) packed_gen_l31_kernel<K, T, ROUNDS, true><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, lp, M, key, chunks, batches);
-        else packed_gen_l31_kernel<K, T, ROUNDS, false><<<dim3(blocks), dim3(kThreads), 0, s>>>(S, n, mod, lp, M, key, chunks, batches);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    const bool vec = gen_vec_ok(L);
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
+        note_kernel("packed_gen_l31_kernel<%d, %d, %d, %s>", K, T, ROUNDS, vec ? "true" : "false");
+        if (vec) packed_gen_l31_kernel<K, T, ROUNDS, true><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, lp, M, key, chunks, batches);
+        else packed_gen_l31_kernel<K, T, ROUNDS, false><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, mod, lp, M, key, chunks, batches);
+        return hipGetLastError();
+    });
 }
 
 template <int KTMAX, int ROUNDS>
@@ -2203,18 +2153,12 @@ static hipError_t packed_l31_launch_rt(const GenLayout& L, uint32_t n, uint32_t 
                                        const L31Params& lp, const MatArg& M, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const bool vec = aligned16(S.out) && S.out_stride_participant % 2 == 0 && S.out_stride_clerk % 2 == 0;
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
         note_kernel("packed_gen_l31_rt_kernel<%d, %d>", KTMAX, ROUNDS);
-        packed_gen_l31_rt_kernel<KTMAX, ROUNDS><<<dim3((unsigned)(chunks * S.participants)), dim3(kThreads), 0, s>>>(
-            S, n, k, t, mod, lp, M, key, chunks, batches, vec);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+        packed_gen_l31_rt_kernel<KTMAX, ROUNDS><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, k, t, mod, lp, M, key, chunks, batches,
+                                                                                                  out_vec_ok(S));
+        return hipGetLastError();
+    });
 }
 
 template <int ROUNDS>
@@ -2234,12 +2178,7 @@ static hipError_t packed_l31_launch_r(const GenLayout& L, uint32_t n, uint32_t k
 hipError_t launch_packed_generate_l31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
                                       const L31Params& lp, const MatArg& M, const DrbgKey& key, int rounds,
                                       hipStream_t s) {
-    switch (rounds) {
-        case 20: return packed_l31_launch_r<20>(L, n, k, t, mod, lp, M, key, s);
-        case 12: return packed_l31_launch_r<12>(L, n, k, t, mod, lp, M, key, s);
-        case 8: return packed_l31_launch_r<8>(L, n, k, t, mod, lp, M, key, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_rounds(rounds, [&](auto R) { return packed_l31_launch_r<decltype(R)::value>(L, n, k, t, mod, lp, M, key, s); });
 }
 
 template <int KTMAX, int ROUNDS>
@@ -2247,18 +2186,12 @@ static hipError_t packed_l31_launch_rtg(const GenLayout& L, uint32_t n, uint32_t
                                         const L31Params& lp, const uint64_t* d_M, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const bool vec = aligned16(S.out) && S.out_stride_participant % 2 == 0 && S.out_stride_clerk % 2 == 0;
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
         note_kernel("packed_gen_l31_rtg_kernel<%d, %d>", KTMAX, ROUNDS);
-        packed_gen_l31_rtg_kernel<KTMAX, ROUNDS><<<dim3((unsigned)(chunks * S.participants)), dim3(kThreads), 0, s>>>(
-            S, n, k, t, mod, lp, d_M, key, chunks, batches, vec);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+        packed_gen_l31_rtg_kernel<KTMAX, ROUNDS><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, k, t, mod, lp, d_M, key, chunks, batches,
+                                                                                                   out_vec_ok(S));
+        return hipGetLastError();
+    });
 }
 
 bool packed_l31_global_path_available(uint32_t k, uint32_t t) { return k >= 1 && k + t <= 64; }
@@ -2268,10 +2201,7 @@ hipError_t launch_packed_generate_l31_global(const GenLayout& L, uint32_t n, uin
                                              const L31Params& lp, const uint64_t* d_M, const DrbgKey& key, int rounds,
                                              hipStream_t s) {
     const uint32_t kt = k + t;
-#define RTG(KTMAX_)                                                                                        \
-    (rounds == 20 ? packed_l31_launch_rtg<KTMAX_, 20>(L, n, k, t, mod, lp, d_M, key, s)                    \
-     : rounds == 12 ? packed_l31_launch_rtg<KTMAX_, 12>(L, n, k, t, mod, lp, d_M, key, s)                  \
-     : rounds == 8 ? packed_l31_launch_rtg<KTMAX_, 8>(L, n, k, t, mod, lp, d_M, key, s) : hipErrorInvalidValue)
+#define RTG(KTMAX_) with_rounds(rounds, [&](auto R) { return packed_l31_launch_rtg<KTMAX_, decltype(R)::value>(L, n, k, t, mod, lp, d_M, key, s); })
     if (kt <= 8) return RTG(8);
     if (kt <= 16) return RTG(16);
     if (kt <= 32) return RTG(32);
@@ -2303,40 +2233,29 @@ static hipError_t packed_mfma_launch_kt(const GenLayout& L, uint32_t n, uint32_t
                                         const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(batches, (uint64_t)kThreads * kMfmaIters);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
         if (mfma_table_bytes<K, T>(n) > 24 * 1024)                      // beyond the default 64 KiB of LDS per workgroup
             if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&packed_gen_mfma_kernel<K, T, ROUNDS>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_table_bytes<K, T>(n)))
                 return e;
         note_kernel("packed_gen_mfma_kernel<%d, %d, %d>", K, T, ROUNDS);
-        packed_gen_mfma_kernel<K, T, ROUNDS><<<dim3((unsigned)(chunks * S.participants)), dim3(kThreads), mfma_table_bytes<K, T>(n), s>>>(
+        packed_gen_mfma_kernel<K, T, ROUNDS><<<dim3((unsigned)blocks), dim3(kThreads), mfma_table_bytes<K, T>(n), s>>>(
             S, n, mod, mont, d_Mbal, key, chunks, batches, kMfmaIters, k, t);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 // d_Mbal: [n][8 * ceil((k + t) / 8)] balanced-byte forms of the Montgomery-form (R = 2^64) matrix, zero padded
 hipError_t launch_packed_generate_mfma(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
                                        const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, int rounds,
                                        hipStream_t s) {
-#define X(K_, T_)                                                                                           \
-    if (k == K_ && t == T_)                                                                                 \
-        return rounds == 20   ? packed_mfma_launch_kt<K_, T_, 20>(L, n, k, t, mod, mont, d_Mbal, key, s)    \
-               : rounds == 12 ? packed_mfma_launch_kt<K_, T_, 12>(L, n, k, t, mod, mont, d_Mbal, key, s)    \
-               : rounds == 8  ? packed_mfma_launch_kt<K_, T_, 8>(L, n, k, t, mod, mont, d_Mbal, key, s)     \
-                              : hipErrorInvalidValue;
+#define KT(K_, T_) with_rounds(rounds, [&](auto R) { return packed_mfma_launch_kt<K_, T_, decltype(R)::value>(L, n, k, t, mod, mont, d_Mbal, key, s); })
+#define X(K_, T_) if (k == K_ && t == T_) return KT(K_, T_);
     SDA_MFMA_SHAPES(X)
 #undef X
     if (!packed_mfma_path_available(k, t, n)) return hipErrorInvalidValue;
-    return rounds == 20   ? packed_mfma_launch_kt<0, 0, 20>(L, n, k, t, mod, mont, d_Mbal, key, s)
-           : rounds == 12 ? packed_mfma_launch_kt<0, 0, 12>(L, n, k, t, mod, mont, d_Mbal, key, s)
-           : rounds == 8  ? packed_mfma_launch_kt<0, 0, 8>(L, n, k, t, mod, mont, d_Mbal, key, s)
-                          : hipErrorInvalidValue;
+    return KT(0, 0);                                                    // run-time (k, t) form
+#undef KT
 }
 
 hipError_t launch_packed_generate_generic(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t,
@@ -2345,44 +2264,31 @@ hipError_t launch_packed_generate_generic(const GenLayout& L, uint32_t n, uint32
     if (!L.rand && t > 0) return hipErrorInvalidValue;
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(batches, kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
         note_kernel("packed_gen_generic_kernel");
-        packed_gen_generic_kernel<<<dim3((unsigned)(chunks * S.participants)), dim3(kThreads), 0, s>>>(S, n, k, t, mod, mont,
-                                                                                                       d_Mmont, chunks, batches);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+        packed_gen_generic_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(S, n, k, t, mod, mont, d_Mmont, chunks, batches);
+        return hipGetLastError();
+    });
 }
 
 template <int ROUNDS>
 static hipError_t drbg_fill_r(int64_t* d_out, size_t stride, size_t participants, size_t batches, uint32_t T,
                               uint64_t first_participant, const ModParams& mod, const DrbgKey& key, hipStream_t s) {
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * participants == 0 || T == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < participants; p0 += per) {
-        const uint64_t cnt = per < participants - p0 ? per : participants - p0;
-        drbg_fill_kernel<ROUNDS><<<dim3((unsigned)(chunks * cnt)), dim3(kThreads), 0, s>>>(d_out + p0 * stride, stride, batches, T,
-                                                                                           first_participant + p0, mod, key, chunks);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    if (T == 0) return hipSuccess;
+    return for_participant_ranges(participants, chunks, kMaxBlocks, [&](uint64_t p0, uint64_t, uint64_t blocks) {
+        drbg_fill_kernel<ROUNDS><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_out + p0 * stride, stride, batches, T,
+                                                                                   first_participant + p0, mod, key, chunks);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_drbg_fill(int64_t* d_out, size_t stride, size_t participants, size_t batches, uint32_t T,
                             uint64_t first_participant, const ModParams& mod, const DrbgKey& key, int rounds,
                             hipStream_t s) {
-    switch (rounds) {
-        case 20: return drbg_fill_r<20>(d_out, stride, participants, batches, T, first_participant, mod, key, s);
-        case 12: return drbg_fill_r<12>(d_out, stride, participants, batches, T, first_participant, mod, key, s);
-        case 8: return drbg_fill_r<8>(d_out, stride, participants, batches, T, first_participant, mod, key, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_rounds(rounds, [&](auto R) {
+        return drbg_fill_r<decltype(R)::value>(d_out, stride, participants, batches, T, first_participant, mod, key, s);
+    });
 }
 
 hipError_t launch_combine_update(uint64_t* d_acc_lo, int64_t* d_acc_hi, const int64_t* d_shares, size_t jobs,
@@ -2432,9 +2338,10 @@ hipError_t launch_combine_update(uint64_t* d_acc_lo, int64_t* d_acc_hi, const in
 }
 
 // ---- dual-role launch ----------------------------------------------------------------------------------
-static bool fuse_plan(const GenLayout& L, uint64_t chunks, uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev,
-                      size_t prev_rows, size_t jobs, size_t dimension, FuseArgs& F) {
-    F.acc_lo = acc_lo; F.acc_hi = acc_hi; F.prev = d_prev;
+static bool fuse_plan(const GenLayout& L, uint64_t chunks, const ClerkSumTarget& C, FuseArgs& F) {
+    const int64_t* d_prev = C.prev;
+    const size_t prev_rows = C.prev_rows, jobs = C.jobs, dimension = C.dimension;
+    F.acc_lo = C.acc_lo; F.acc_hi = C.acc_hi; F.prev = d_prev;
     F.job_stride = L.out_stride_clerk; F.row_stride = L.out_stride_participant;
     F.n_rows = prev_rows; F.dimension = dimension; F.jobs = (uint32_t)jobs;
     F.n_gen = chunks * L.participants;
@@ -2454,7 +2361,7 @@ static bool fuse_plan(const GenLayout& L, uint64_t chunks, uint64_t* acc_lo, int
     if (F.n_comb && (F.period & 1) == 0) F.period = F.period > 2 ? F.period - 1 : 3;
     F.grid = F.n_gen + F.n_comb;
     if (F.n_comb && (F.n_comb - 1) * F.period + 1 > F.grid) F.grid = (F.n_comb - 1) * F.period + 1;   // surplus positions idle
-    const bool fused = F.grid != 0 && F.grid <= kMaxBlocks && (!F.n_gen || gen_vec_ok(L, 0)) &&
+    const bool fused = F.grid != 0 && F.grid <= kMaxBlocks && (!F.n_gen || gen_vec_ok(L)) &&
                        (!have_comb || (aligned16(d_prev) && (F.job_stride % 2 == 0) && (F.row_stride % 2 == 0)));
     const unsigned long long plan[8] = {fused, F.n_gen, F.n_comb, F.period, F.grid, F.splits, F.rows_per_split, F.col_blocks};
     note_fuse_plan(plan);                                           // host only: sda_debug_last_fuse_plan (test library)
@@ -2474,21 +2381,18 @@ static hipError_t fused_l31_kt(const GenLayout& L, uint32_t n, const ModParams& 
 #define SDA_FUSED_SHAPES(X) X(3, 1) X(3, 4) X(8, 2) X(8, 7)
 
 hipError_t launch_fused_packed_l31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
-                                   const L31Params& lp, const MatArg& M, const DrbgKey& key, int rounds, uint64_t* acc_lo,
-                                   int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs, size_t dimension,
+                                   const L31Params& lp, const MatArg& M, const DrbgKey& key, int rounds, const ClerkSumTarget& C,
                                    hipStream_t s, bool* fused) {
     *fused = false;
-    if ((rounds != 20 && rounds != 12 && rounds != 8) || L.rand) return hipSuccess;
+    if (!rounds_supported(rounds) || L.rand) return hipSuccess;
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
     FuseArgs F;
-    if (!fuse_plan(L, chunks, acc_lo, acc_hi, d_prev, prev_rows, jobs, dimension, F)) return hipSuccess;
+    if (!fuse_plan(L, chunks, C, F)) return hipSuccess;
 #define X(K_, T_)                                                                                                        \
     if (k == K_ && t == T_) {                                                                                            \
         *fused = true;                                                                                                   \
-        return rounds == 20 ? fused_l31_kt<K_, T_, 20>(L, n, mod, lp, M, key, F, chunks, batches, s)                     \
-             : rounds == 12 ? fused_l31_kt<K_, T_, 12>(L, n, mod, lp, M, key, F, chunks, batches, s)                     \
-                            : fused_l31_kt<K_, T_, 8>(L, n, mod, lp, M, key, F, chunks, batches, s);                     \
+        return with_rounds(rounds, [&](auto R) { return fused_l31_kt<K_, T_, decltype(R)::value>(L, n, mod, lp, M, key, F, chunks, batches, s); }); \
     }
     SDA_FUSED_SHAPES(X)
 #undef X
@@ -2498,15 +2402,13 @@ hipError_t launch_fused_packed_l31(const GenLayout& L, uint32_t n, uint32_t k, u
     *fused = true;
     const dim3 grid((unsigned)F.grid), block(kThreads);
 #define RT(KTMAX_)                                                                                                      \
-    do {                                                                                                                 \
+    with_rounds(rounds, [&](auto R) {                                                                                    \
         note_kernel("fused_packed_l31_rt_kernel<%d, %d>", KTMAX_, rounds);                                               \
-        if (rounds == 20) fused_packed_l31_rt_kernel<KTMAX_, 20><<<grid, block, 0, s>>>(L, n, k, t, mod, lp, M, key, chunks, batches, F); \
-        else if (rounds == 12) fused_packed_l31_rt_kernel<KTMAX_, 12><<<grid, block, 0, s>>>(L, n, k, t, mod, lp, M, key, chunks, batches, F); \
-        else fused_packed_l31_rt_kernel<KTMAX_, 8><<<grid, block, 0, s>>>(L, n, k, t, mod, lp, M, key, chunks, batches, F); \
-    } while (0)
-    if (kt <= 4) RT(4); else if (kt <= 8) RT(8); else if (kt <= 12) RT(12); else RT(16);
+        fused_packed_l31_rt_kernel<KTMAX_, decltype(R)::value><<<grid, block, 0, s>>>(L, n, k, t, mod, lp, M, key, chunks, batches, F); \
+        return hipGetLastError();                                                                                        \
+    })
+    return kt <= 4 ? RT(4) : kt <= 8 ? RT(8) : kt <= 12 ? RT(12) : RT(16);
 #undef RT
-    return hipGetLastError();
 }
 
 static constexpr uint32_t kMfmaFusedIters = 2;                 // 512 batches per share-gen item, as in the limb-31 dual-role launch
@@ -2526,28 +2428,21 @@ static hipError_t fused_mfma_kt(const GenLayout& L, uint32_t n, uint32_t k, uint
 }
 
 hipError_t launch_fused_packed_mfma(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod,
-                                    const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, int rounds, uint64_t* acc_lo,
-                                    int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs, size_t dimension,
-                                    hipStream_t s, bool* fused) {
+                                    const MontParams& mont, const uint64_t* d_Mbal, const DrbgKey& key, int rounds,
+                                    const ClerkSumTarget& C, hipStream_t s, bool* fused) {
     *fused = false;
-    if ((rounds != 20 && rounds != 12 && rounds != 8) || L.rand || !packed_mfma_path_available(k, t, n)) return hipSuccess;
+    if (!rounds_supported(rounds) || L.rand || !packed_mfma_path_available(k, t, n)) return hipSuccess;
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(batches, (uint64_t)kThreads * kMfmaFusedIters);
     FuseArgs F;
-    if (!fuse_plan(L, chunks, acc_lo, acc_hi, d_prev, prev_rows, jobs, dimension, F)) return hipSuccess;
-#define X(K_, T_)                                                                                                        \
-    if (k == K_ && t == T_) {                                                                                            \
-        *fused = true;                                                                                                   \
-        return rounds == 20 ? fused_mfma_kt<K_, T_, 20>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s)       \
-             : rounds == 12 ? fused_mfma_kt<K_, T_, 12>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s)       \
-                            : fused_mfma_kt<K_, T_, 8>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s);       \
-    }
+    if (!fuse_plan(L, chunks, C, F)) return hipSuccess;
+    *fused = true;                                                      // every shape left has an instance
+#define KT(K_, T_) with_rounds(rounds, [&](auto R) { return fused_mfma_kt<K_, T_, decltype(R)::value>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s); })
+#define X(K_, T_) if (k == K_ && t == T_) return KT(K_, T_);
     SDA_MFMA_SHAPES(X)
 #undef X
-    *fused = true;                                                      // run-time (k, t) form
-    return rounds == 20 ? fused_mfma_kt<0, 0, 20>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s)
-         : rounds == 12 ? fused_mfma_kt<0, 0, 12>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s)
-                        : fused_mfma_kt<0, 0, 8>(L, n, k, t, mod, mont, d_Mbal, key, F, chunks, batches, s);
+    return KT(0, 0);                                                    // run-time (k, t) form
+#undef KT
 }
 
 // ---- narrow-modulus kernels (narrow_gen.inc.hpp) ---------------------------------------------------------------------
@@ -2571,27 +2466,20 @@ hipError_t launch_packed_generate_n31(const GenLayout& L, uint32_t n, uint32_t k
                                       const N31Params& np, const MatArg& M, const DrbgKey& key, hipStream_t s) {
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
-    if (chunks * L.participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, L.participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < L.participants; p0 += per) {
-        const GenLayout S = slice(L, p0, per < L.participants - p0 ? per : L.participants - p0);
-        const bool vec = aligned16(S.out) && S.out_stride_participant % 2 == 0 && S.out_stride_clerk % 2 == 0;
-        SDA_N31_DISPATCH(packed_gen_n31_kernel, chunks * S.participants, S, n, k, t, mod, np, M, key, chunks, batches, vec);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return for_participant_slices(L, chunks, kMaxBlocks, [&](const GenLayout& S, uint64_t blocks) {
+        SDA_N31_DISPATCH(packed_gen_n31_kernel, blocks, S, n, k, t, mod, np, M, key, chunks, batches, out_vec_ok(S));
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fused_packed_n31(const GenLayout& L, uint32_t n, uint32_t k, uint32_t t, const ModParams& mod, const N31Params& np,
-                                   const MatArg& M, const DrbgKey& key, uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev,
-                                   size_t prev_rows, size_t jobs, size_t dimension, hipStream_t s, bool* fused) {
+                                   const MatArg& M, const DrbgKey& key, const ClerkSumTarget& C, hipStream_t s, bool* fused) {
     *fused = false;
     if (L.rand) return hipSuccess;
     const uint64_t batches = ceil_div(L.len, k);
     const uint64_t chunks = ceil_div(ceil_div(batches, 2), kThreads);
     FuseArgs F;
-    if (!fuse_plan(L, chunks, acc_lo, acc_hi, d_prev, prev_rows, jobs, dimension, F)) return hipSuccess;
+    if (!fuse_plan(L, chunks, C, F)) return hipSuccess;
     *fused = true;
     SDA_N31_DISPATCH(fused_packed_n31_kernel, F.grid, L, n, k, t, mod, np, M, key, chunks, batches, F);
     return hipGetLastError();
@@ -2599,20 +2487,18 @@ hipError_t launch_fused_packed_n31(const GenLayout& L, uint32_t n, uint32_t k, u
 #undef SDA_N31_DISPATCH
 
 hipError_t launch_fused_additive(const GenLayout& L, uint32_t n, const ModParams& mod, const DrbgKey& key, int rounds,
-                                 uint64_t* acc_lo, int64_t* acc_hi, const int64_t* d_prev, size_t prev_rows, size_t jobs,
-                                 size_t dimension, hipStream_t s, bool* fused) {
+                                 const ClerkSumTarget& C, hipStream_t s, bool* fused) {
     *fused = false;
-    if ((rounds != 20 && rounds != 12 && rounds != 8) || L.rand) return hipSuccess;
+    if (!rounds_supported(rounds) || L.rand) return hipSuccess;
     const uint64_t chunks = ceil_div(ceil_div(L.len, 2), kThreads);
     FuseArgs F;
-    if (!fuse_plan(L, chunks, acc_lo, acc_hi, d_prev, prev_rows, jobs, dimension, F)) return hipSuccess;
+    if (!fuse_plan(L, chunks, C, F)) return hipSuccess;
     *fused = true;
-    const dim3 grid((unsigned)F.grid), block(kThreads);
     note_kernel("fused_additive_kernel<%d>", rounds);
-    if (rounds == 20) fused_additive_kernel<20><<<grid, block, 0, s>>>(L, n, mod, key, chunks, F);
-    else if (rounds == 12) fused_additive_kernel<12><<<grid, block, 0, s>>>(L, n, mod, key, chunks, F);
-    else fused_additive_kernel<8><<<grid, block, 0, s>>>(L, n, mod, key, chunks, F);
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto R) {
+        fused_additive_kernel<decltype(R)::value><<<dim3((unsigned)F.grid), dim3(kThreads), 0, s>>>(L, n, mod, key, chunks, F);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_combine_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, size_t count, const ModParams& mod,
@@ -2741,20 +2627,16 @@ hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride
     uint64_t per = 0xFFFFFFFFull / (blocks * kThreads);
     if (per > 65535) per = 65535;
     if (per == 0) return hipErrorInvalidConfiguration;
-    for (size_t p0 = 0; p0 < participants; p0 += per) {
-        const unsigned np = (unsigned)(participants - p0 < per ? participants - p0 : per);
-        const dim3 grid((unsigned)blocks, np);
-        const int64_t* sp = d_secrets + p0 * secrets_stride;
-        int64_t* mp = d_mask + p0 * mask_stride;
-        int64_t* xp = d_masked + p0 * masked_stride;
-        switch (rounds) {
-            case 20: full_mask_drbg_kernel<20><<<grid, dim3(kThreads), 0, s>>>(sp, secrets_stride, len, first_stream + p0, mod, key, mp, mask_stride, xp, masked_stride, vec); break;
-            case 12: full_mask_drbg_kernel<12><<<grid, dim3(kThreads), 0, s>>>(sp, secrets_stride, len, first_stream + p0, mod, key, mp, mask_stride, xp, masked_stride, vec); break;
-            case 8: full_mask_drbg_kernel<8><<<grid, dim3(kThreads), 0, s>>>(sp, secrets_stride, len, first_stream + p0, mod, key, mp, mask_stride, xp, masked_stride, vec); break;
-            default: return hipErrorInvalidValue;
+    return with_rounds(rounds, [&](auto R) {
+        for (size_t p0 = 0; p0 < participants; p0 += per) {
+            const unsigned np = (unsigned)(participants - p0 < per ? participants - p0 : per);
+            full_mask_drbg_kernel<decltype(R)::value><<<dim3((unsigned)blocks, np), dim3(kThreads), 0, s>>>(
+                d_secrets + p0 * secrets_stride, secrets_stride, len, first_stream + p0, mod, key, d_mask + p0 * mask_stride, mask_stride,
+                d_masked + p0 * masked_stride, masked_stride, vec);
+            if (hipError_t e = hipGetLastError()) return e;
         }
-    }
-    return hipGetLastError();
+        return hipSuccess;
+    });
 }
 
 hipError_t launch_chacha_mask_accumulate(const uint32_t* d_seeds, const uint32_t* d_n_seeds, size_t max_seeds, size_t dimension,
@@ -2824,7 +2706,7 @@ hipError_t launch_chacha_mask_shift_listed(const uint32_t* d_seeds, const uint32
         if (gy < 16) gy = 16;
         if (gy > max_list) gy = max_list;
     } else {            // no caller today: the one driver plans every shift list on the device
-        gy = participants_per_launch(pos_blocks, max_list);
+        gy = participants_per_launch(pos_blocks, max_list, kMaxBlocks);
     }
     if (gy > 65535) gy = 65535;
     const dim3 grid((unsigned)pos_blocks, (unsigned)gy);
@@ -2870,8 +2752,9 @@ hipError_t launch_chacha_apply_fast(const uint32_t* d_seeds, size_t participants
                            apply.out_stride, apply.mod};
         chacha_mask_apply_kernel<<<dim3((unsigned)pos_blocks, np), dim3(kThreads), 0, s>>>(d_seeds + p0 * 8, dimension, zone,
                                                                                          d_rejects + p0, ap);
+        if (hipError_t e = hipGetLastError()) return e;
     }
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 hipError_t launch_modsum_parts(const int64_t* d_parts, size_t parts, size_t part_stride, size_t len,
@@ -2886,16 +2769,11 @@ hipError_t launch_modsum_parts(const int64_t* d_parts, size_t parts, size_t part
 hipError_t launch_fill_synthetic(int64_t* d_out, size_t participants, size_t len, size_t stride,
                                  uint64_t first_participant, uint64_t seed, const ModParams& mod, hipStream_t s) {
     const uint64_t chunks = ceil_div(len, kThreads);
-    if (chunks * participants == 0) return hipSuccess;
-    const uint64_t per = participants_per_launch(chunks, participants);
-    if (per == 0) return hipErrorInvalidConfiguration;
-    for (uint64_t p0 = 0; p0 < participants; p0 += per) {
-        const uint64_t cnt = per < participants - p0 ? per : participants - p0;
-        fill_synthetic_kernel<<<dim3((unsigned)(chunks * cnt)), dim3(kThreads), 0, s>>>(d_out + p0 * stride, len, stride,
-                                                                                        first_participant + p0, seed, mod, chunks);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return for_participant_ranges(participants, chunks, kMaxBlocks, [&](uint64_t p0, uint64_t, uint64_t blocks) {
+        fill_synthetic_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(d_out + p0 * stride, len, stride, first_participant + p0,
+                                                                                seed, mod, chunks);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace sda

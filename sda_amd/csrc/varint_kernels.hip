@@ -15,6 +15,7 @@
 #include "capi_internal.hpp"
 #include "drbg_quad.hpp"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 #include "modarith.hpp"
 #include "sbox_primitives.hpp"
 
@@ -1514,13 +1515,10 @@ hipError_t launch_share_seal_stream(const ShareJob& J, int rounds, uint8_t* d_bo
     const uint64_t groups = by_rows ? vceil((uint64_t)J.n * J.participants, kStreamWaves) : vceil(J.n, kStreamWaves) * (uint64_t)J.participants;
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     const dim3 grid((unsigned)groups), block(kStreamWaves * 64);
-    switch (rounds) {
-        case 20: share_seal_stream_kernel<20><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        case 12: share_seal_stream_kernel<12><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        case 8: share_seal_stream_kernel<8><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto R) {
+        share_seal_stream_kernel<decltype(R)::value><<<grid, block, 0, s>>>(J, by_rows, d_boxes, slot_bytes, d_states, d_msg_bytes);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_mask_seal_stream(const MaskJob& J, int rounds, uint8_t* d_boxes, size_t slot_bytes, const SboxState* d_states,
@@ -1529,13 +1527,10 @@ hipError_t launch_mask_seal_stream(const MaskJob& J, int rounds, uint8_t* d_boxe
     const uint64_t groups = vceil(J.participants, kStreamWaves);
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     const dim3 grid((unsigned)groups), block(kStreamWaves * 64);
-    switch (rounds) {
-        case 20: mask_seal_stream_kernel<20><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        case 12: mask_seal_stream_kernel<12><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        case 8: mask_seal_stream_kernel<8><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_rounds(rounds, [&](auto R) {
+        mask_seal_stream_kernel<decltype(R)::value><<<grid, block, 0, s>>>(J, d_boxes, slot_bytes, d_states, d_msg_bytes);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_varint_stream_combine(const uint8_t* d_bytes, size_t n_bytes, const RowRanges& d_offsets, size_t jobs,
