@@ -101,6 +101,11 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(capi.c_i64p)
 
 
+def _index_array(indices: Optional[Sequence[int]]):
+    """clerk indices as a size_t array for the C ABI (never of length 0); None stays None"""
+    return None if indices is None else (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
+
+
 def _rows(vectors: Sequence) -> Tuple[List[np.ndarray], C.Array, C.Array]:
     if isinstance(vectors, np.ndarray) and vectors.ndim == 2 and vectors.dtype == np.int64 and vectors.shape[0] > 0 \
             and vectors.strides[1] == 8:
@@ -415,6 +420,7 @@ class RevealCheck(NamedTuple):
     corrected: int
     first_bad: Optional[int]
     blame: Tuple[int, ...]
+    HEAD = 4                         # report words before the blame
 
     @property
     def clean(self) -> bool:
@@ -423,7 +429,7 @@ class RevealCheck(NamedTuple):
     @classmethod
     def from_words(cls, words: Sequence[int]) -> "RevealCheck":
         w = [int(x) & 0xFFFFFFFFFFFFFFFF for x in words]
-        return cls(w[0], w[1], w[2], None if w[3] == 0xFFFFFFFFFFFFFFFF else w[3], tuple(w[4:]))
+        return cls(w[0], w[1], w[2], None if w[3] == 0xFFFFFFFFFFFFFFFF else w[3], tuple(w[cls.HEAD:]))
 
 
 class RevealDecode(NamedTuple):
@@ -438,6 +444,7 @@ class RevealDecode(NamedTuple):
     most: int
     by_count: Tuple[int, ...]
     blame: Tuple[int, ...]
+    HEAD = 16                        # report words before the blame
 
     @property
     def clean(self) -> bool:
@@ -451,7 +458,7 @@ class RevealDecode(NamedTuple):
     def from_words(cls, words: Sequence[int]) -> "RevealDecode":
         w = [int(x) & 0xFFFFFFFFFFFFFFFF for x in words]
         none = 0xFFFFFFFFFFFFFFFF
-        return cls(w[0], w[1], w[2], None if w[3] == none else w[3], None if w[4] == none else w[4], w[5], tuple(w[8:16]), tuple(w[16:]))
+        return cls(w[0], w[1], w[2], None if w[3] == none else w[3], None if w[4] == none else w[4], w[5], tuple(w[8:cls.HEAD]), tuple(w[cls.HEAD:]))
 
 
 class SecretReconstructor(_Handle):
@@ -467,9 +474,8 @@ class SecretReconstructor(_Handle):
         check(self._lib.sda_secret_reconstructor_new(C.byref(cs), dimension, C.byref(self._h)))
 
     def reconstruct(self, indexed_shares: Sequence[Tuple[int, Sequence]]) -> np.ndarray:
-        idx = [int(i) for i, _ in indexed_shares]
         arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
-        cidx = (C.c_size_t * max(len(idx), 1))(*idx)
+        cidx = _index_array([i for i, _ in indexed_shares])
         cap = max(self.dimension, arrs[0].size if arrs else 0)
         out = np.empty(max(cap, 1), dtype=np.int64)
         n_out = C.c_size_t()
@@ -479,9 +485,8 @@ class SecretReconstructor(_Handle):
 
     def reconstruct_dev(self, indices: Sequence[int], d_shares: int, row_len: int, row_stride: int, d_out: int,
                         out_cap: int, stream: int = 0) -> int:
-        cidx = (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
         n_out = C.c_size_t()
-        check(self._lib.sda_secret_reconstructor_reconstruct_dev(self._h, cidx, len(indices), d_shares, row_len,
+        check(self._lib.sda_secret_reconstructor_reconstruct_dev(self._h, _index_array(indices), len(indices), d_shares, row_len,
                                                                  row_stride, d_out, out_cap, C.byref(n_out),
                                                                  stream or None))
         return n_out.value
@@ -489,10 +494,12 @@ class SecretReconstructor(_Handle):
     # streaming device form (receive.rs:120-146 with the clerking results in HBM): no update synchronises or copies to the host
     def begin_dev(self, indices: Optional[Sequence[int]], n_rows: int, row_len: int, stream: int = 0) -> None:
         """declares the job: indices[i] is the clerk index of position i (Additive: None), every row holds row_len values"""
+        check(self._lib.sda_secret_reconstructor_begin_dev(self._h, self._job_indices(indices, n_rows), n_rows, row_len, stream or None))
+
+    def _job_indices(self, indices: Optional[Sequence[int]], n_rows: int):
         if indices is not None and len(indices) != n_rows:
             raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {n_rows} rows")
-        cidx = None if indices is None else (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
-        check(self._lib.sda_secret_reconstructor_begin_dev(self._h, cidx, n_rows, row_len, stream or None))
+        return _index_array(indices)
 
     def update_dev(self, first_pos: int, d_shares: int, rows: int, row_stride: int, stream: int = 0) -> None:
         """decoded rows in HBM for positions first_pos .. first_pos + rows - 1"""
@@ -519,9 +526,7 @@ class SecretReconstructor(_Handle):
 
     def begin_checked_dev(self, indices: Sequence[int], n_rows: int, row_len: int, checks: int, stream: int = 0) -> None:
         """begin_dev with `checks` parity columns behind the k secret columns; update_dev / update_sealed_rows_dev feed it"""
-        if indices is not None and len(indices) != n_rows:
-            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {n_rows} rows")
-        cidx = None if indices is None else (C.c_size_t * max(len(indices), 1))(*[int(i) for i in indices])
+        cidx = self._job_indices(indices, n_rows)
         check(self._lib.sda_secret_reconstructor_begin_checked_dev(self._h, cidx, n_rows, row_len, checks, stream or None))
 
     def finish_checked_dev(self, d_out: int, out_cap: int, d_report: int, correct: bool = False, stream: int = 0) -> None:
@@ -533,36 +538,54 @@ class SecretReconstructor(_Handle):
     def reconstruct_checked(self, indexed_shares: Sequence[Tuple[int, Sequence]], checks: Optional[int] = None,
                             correct: bool = False) -> Tuple[np.ndarray, "RevealCheck"]:
         """reconstruct() that also says whether the rows agree: (values, RevealCheck)"""
-        idx = [int(i) for i, _ in indexed_shares]
+        return self._reconstruct_with_checks(RevealCheck, indexed_shares, checks, 0, correct)
+
+    def _reconstruct_with_checks(self, kind, indexed_shares, checks: Optional[int], max_errors: int, correct: bool):
+        """reconstruct_checked (kind RevealCheck; max_errors is not read) and reconstruct_decoded (RevealDecode)"""
         arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
-        cidx = (C.c_size_t * max(len(idx), 1))(*idx)
+        cidx = _index_array([i for i, _ in indexed_shares])
         if checks is None and not isinstance(self.scheme, Additive):
             checks = self.default_checks(len(arrs))
         out = np.empty(max(self.dimension, 1), dtype=np.int64)
-        report = (C.c_uint64 * (4 + len(arrs)))()
+        report = (C.c_uint64 * (kind.HEAD + len(arrs)))()
         n_out = C.c_size_t()
-        check(self._lib.sda_secret_reconstructor_reconstruct_checked(
-            self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0), capi.CHECK_CORRECT if correct else capi.CHECK_REPORT,
-            _ptr(out), self.dimension, C.byref(n_out), report))
-        return out[:n_out.value].copy(), RevealCheck.from_words(list(report))
+        head = (self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0))
+        tail = (capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, _ptr(out), self.dimension, C.byref(n_out), report)
+        if kind is RevealCheck:
+            check(self._lib.sda_secret_reconstructor_reconstruct_checked(*head, *tail))
+        else:
+            check(self._lib.sda_secret_reconstructor_reconstruct_decoded(*head, max_errors, *tail))
+        return out[:n_out.value].copy(), kind.from_words(list(report))
 
     def reconstruct_sealed_job_checked(self, blob, indices: Sequence[int], pk: bytes, sk: bytes, checks: Optional[int] = None,
                                        correct: bool = False) -> Tuple[np.ndarray, "RevealCheck"]:
         """reconstruct_sealed_job with the checks riding along: (values, RevealCheck).  A bad box still fails the reveal
         (sodium.rs:78-80) - the check is for results that open and disagree"""
+        return self._reconstruct_sealed_job_with_checks(RevealCheck, "reconstruct_sealed_job_checked", blob, indices, pk, sk, checks, 0, correct)
+
+    def _reconstruct_sealed_job_with_checks(self, kind, name: str, blob, indices, pk, sk, checks, max_errors: int, correct: bool):
+        """reconstruct_sealed_job_checked (kind RevealCheck; max_errors is not read) and reconstruct_sealed_job_decoded (RevealDecode)"""
         from .device import DeviceBuffer
-        job = _parse_sealed_job("reconstruct_sealed_job_checked", blob)
+        job = _parse_sealed_job(name, blob)
         row_len, n_out = self._sealed_job_shape(None)
         rows = job.layout.rows
         checks = self.default_checks(rows) if checks is None else checks
-        # [0]: the status word, [1 .. 5 + rows): the report, then the output
-        d_buf = DeviceBuffer(1 + 4 + rows + max(n_out, 1)).zero()
+        # [0]: the status word, [1 .. first): the report, then the output
+        first = 1 + kind.HEAD + rows
+        d_buf = DeviceBuffer(first + max(n_out, 1)).zero()
         held = self._feed_sealed_job(job, indices, row_len, pk, sk, d_buf.at(0), checks=checks)
-        self.finish_checked_dev(d_buf.at(5 + rows), n_out, d_buf.at(1), correct)
+        self._finish_with_checks(kind, d_buf.at(first), n_out, d_buf.at(1), max_errors, correct)
         back = d_buf.to_numpy()
         del held
         _raise_sealed_status(int(back[0]))
-        return back[5 + rows:5 + rows + n_out].copy(), RevealCheck.from_words(back[1:5 + rows].view(np.uint64).tolist())
+        return back[first:first + n_out].copy(), kind.from_words(back[1:first].view(np.uint64).tolist())
+
+    def _finish_with_checks(self, kind, d_out: int, out_cap: int, d_report: int, max_errors: int, correct: bool) -> None:
+        """finish_checked_dev (kind RevealCheck; max_errors is not read) or finish_decoded_dev (RevealDecode)"""
+        if kind is RevealCheck:
+            self.finish_checked_dev(d_out, out_cap, d_report, correct)
+        else:
+            self.finish_decoded_dev(d_out, out_cap, d_report, max_errors, correct)
 
     # the decoding finish of a checked job: up to floor(checks / 2) disagreeing clerking results per batch, named and repaired
     def finish_decoded_dev(self, d_out: int, out_cap: int, d_report: int, max_errors: int = 0, correct: bool = False,
@@ -576,36 +599,13 @@ class SecretReconstructor(_Handle):
     def reconstruct_decoded(self, indexed_shares: Sequence[Tuple[int, Sequence]], checks: Optional[int] = None, max_errors: int = 0,
                             correct: bool = False) -> Tuple[np.ndarray, "RevealDecode"]:
         """reconstruct_checked with the decoding finish: (values, RevealDecode)"""
-        idx = [int(i) for i, _ in indexed_shares]
-        arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
-        cidx = (C.c_size_t * max(len(idx), 1))(*idx)
-        if checks is None and not isinstance(self.scheme, Additive):
-            checks = self.default_checks(len(arrs))
-        out = np.empty(max(self.dimension, 1), dtype=np.int64)
-        report = (C.c_uint64 * (16 + len(arrs)))()
-        n_out = C.c_size_t()
-        check(self._lib.sda_secret_reconstructor_reconstruct_decoded(
-            self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0), max_errors,
-            capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, _ptr(out), self.dimension, C.byref(n_out), report))
-        return out[:n_out.value].copy(), RevealDecode.from_words(list(report))
+        return self._reconstruct_with_checks(RevealDecode, indexed_shares, checks, max_errors, correct)
 
     def reconstruct_sealed_job_decoded(self, blob, indices: Sequence[int], pk: bytes, sk: bytes, checks: Optional[int] = None,
                                        max_errors: int = 0, correct: bool = False) -> Tuple[np.ndarray, "RevealDecode"]:
         """reconstruct_sealed_job_checked with the decoding finish: (values, RevealDecode).  A bad box still fails the reveal
         (sodium.rs:78-80)"""
-        from .device import DeviceBuffer
-        job = _parse_sealed_job("reconstruct_sealed_job_decoded", blob)
-        row_len, n_out = self._sealed_job_shape(None)
-        rows = job.layout.rows
-        checks = self.default_checks(rows) if checks is None else checks
-        # [0]: the status word, [1 .. 17 + rows): the report, then the output
-        d_buf = DeviceBuffer(1 + 16 + rows + max(n_out, 1)).zero()
-        held = self._feed_sealed_job(job, indices, row_len, pk, sk, d_buf.at(0), checks=checks)
-        self.finish_decoded_dev(d_buf.at(17 + rows), n_out, d_buf.at(1), max_errors, correct)
-        back = d_buf.to_numpy()
-        del held
-        _raise_sealed_status(int(back[0]))
-        return back[17 + rows:17 + rows + n_out].copy(), RevealDecode.from_words(back[1:17 + rows].view(np.uint64).tolist())
+        return self._reconstruct_sealed_job_with_checks(RevealDecode, "reconstruct_sealed_job_decoded", blob, indices, pk, sk, checks, max_errors, correct)
 
     def reconstruct_sealed_job(self, blob, indices: Optional[Sequence[int]], pk: bytes, sk: bytes,
                                row_len: Optional[int] = None) -> np.ndarray:
@@ -946,6 +946,22 @@ def participate_sealed(aggregation: Aggregation, secrets_2d, recipient_pk: bytes
     return mask_job, jobs_of(d_boxes, d_lens, slot, n)
 
 
+def _parse_reveal_jobs(name: str, masking_scheme, mask_job, result_job, recipient_pk: bytes, recipient_sk: bytes):
+    """the front of every reveal from wire bytes: the keys are 32 bytes, a mask job comes with a scheme that has masks and only
+    then, both blobs parse -> (the mask job or None, the results' job)"""
+    if len(recipient_pk) != 32 or len(recipient_sk) != 32:
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
+    if masking_scheme.has_mask() != (mask_job is not None):
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
+    return _parse_sealed_job(name, mask_job) if mask_job is not None else None, _parse_sealed_job(name, result_job)
+
+
+def _check_result_indices(indices: Optional[Sequence[int]], rows: int, optional: bool) -> None:
+    """one clerk index per clerking result; optional (Additive): None is as good"""
+    if (indices is None and not optional) or (indices is not None and len(indices) != rows):
+        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{0 if indices is None else len(indices)} indices for {rows} clerking results")
+
+
 def reveal_sealed(aggregation: Aggregation, mask_job, result_job, indices: Optional[Sequence[int]], recipient_pk: bytes,
                   recipient_sk: bytes) -> RecipientOutput:
     """reveal_aggregation (receive.rs:80-157) from wire bytes, the counterpart of participate_sealed and
@@ -957,18 +973,8 @@ def reveal_sealed(aggregation: Aggregation, mask_job, result_job, indices: Optio
     from .device import DeviceBuffer
     a = aggregation
     sch, msch = a.committee_sharing_scheme, a.masking_scheme
-    if len(recipient_pk) != 32 or len(recipient_sk) != 32:
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
-    if msch.has_mask() != (mask_job is not None):
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
-    masks = _parse_sealed_job("reveal_sealed", mask_job) if mask_job is not None else None
-    results = _parse_sealed_job("reveal_sealed", result_job)
-    additive = isinstance(sch, Additive)
-    if not additive and (indices is None or len(indices) != results.layout.rows):
-        raise SdaError(capi.ERR_INVALID_ARGUMENT,
-                       f"{0 if indices is None else len(indices)} indices for {results.layout.rows} clerking results")
-    if additive and indices is not None and len(indices) != results.layout.rows:
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(indices)} indices for {results.layout.rows} clerking results")
+    masks, results = _parse_reveal_jobs("reveal_sealed", msch, mask_job, result_job, recipient_pk, recipient_sk)
+    _check_result_indices(indices, results.layout.rows, optional=isinstance(sch, Additive))
     reconstructor = SecretReconstructor(sch, a.vector_dimension)
     row_len, n_out = reconstructor._sealed_job_shape(None)
     unmasker = SecretUnmasker(msch)
@@ -993,8 +999,8 @@ def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indice
     SecretReconstructor.finish_checked_dev + SecretUnmasker.unmask_dev - the one-kernel unmask_jobs_dev reads a plain job only.
     Returns (RecipientOutput, RevealCheck); correct=True repairs every batch that one clerking result alone spoils.  The failures of
     reveal_sealed stay: a bad box fails the reveal whatever the check says (sodium.rs:78-80)."""
-    return _reveal_sealed_with_checks("reveal_sealed_checked", aggregation, mask_job, result_job, indices, recipient_pk, recipient_sk,
-                                      checks, None, correct)
+    return _reveal_sealed_with_checks(RevealCheck, "reveal_sealed_checked", aggregation, mask_job, result_job, indices, recipient_pk,
+                                      recipient_sk, checks, 0, correct)
 
 
 def reveal_sealed_decoded(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
@@ -1002,27 +1008,22 @@ def reveal_sealed_decoded(aggregation: Aggregation, mask_job, result_job, indice
     """reveal_sealed_checked with SecretReconstructor.finish_decoded_dev in the chain: up to max_errors (0: floor(checks / 2))
     disagreeing clerking results per batch are named and, with correct=True, repaired.  Returns (RecipientOutput, RevealDecode).
     A bad box still fails the reveal (sodium.rs:78-80)."""
-    return _reveal_sealed_with_checks("reveal_sealed_decoded", aggregation, mask_job, result_job, indices, recipient_pk, recipient_sk,
-                                      checks, max_errors, correct)
+    return _reveal_sealed_with_checks(RevealDecode, "reveal_sealed_decoded", aggregation, mask_job, result_job, indices, recipient_pk,
+                                      recipient_sk, checks, max_errors, correct)
 
 
-def _reveal_sealed_with_checks(name: str, aggregation: Aggregation, mask_job, result_job, indices, recipient_pk: bytes, recipient_sk: bytes,
-                               checks: Optional[int], max_errors: Optional[int], correct: bool):
-    """the chain of reveal_sealed_checked (max_errors None: finish_checked_dev) and reveal_sealed_decoded (finish_decoded_dev)"""
+def _reveal_sealed_with_checks(kind, name: str, aggregation: Aggregation, mask_job, result_job, indices, recipient_pk: bytes,
+                               recipient_sk: bytes, checks: Optional[int], max_errors: int, correct: bool):
+    """the chain of reveal_sealed_checked (kind RevealCheck: finish_checked_dev, max_errors is not read) and reveal_sealed_decoded
+    (RevealDecode: finish_decoded_dev)"""
     from .device import DeviceBuffer
     a = aggregation
     sch, msch = a.committee_sharing_scheme, a.masking_scheme
-    if len(recipient_pk) != 32 or len(recipient_sk) != 32:
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, "the recipient's keys are 32 bytes each")
-    if msch.has_mask() != (mask_job is not None):
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, "a mask job goes with a masking scheme that has masks, None with NoMask")
-    masks = _parse_sealed_job(name, mask_job) if mask_job is not None else None
-    results = _parse_sealed_job(name, result_job)
+    masks, results = _parse_reveal_jobs(name, msch, mask_job, result_job, recipient_pk, recipient_sk)
     if isinstance(sch, Additive):
         raise SdaError(capi.ERR_UNSUPPORTED, "additive sharing has no redundancy to check")
     rows = results.layout.rows
-    if indices is None or len(indices) != rows:
-        raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{0 if indices is None else len(indices)} indices for {rows} clerking results")
+    _check_result_indices(indices, rows, optional=False)
     reconstructor = SecretReconstructor(sch, a.vector_dimension)
     row_len, n_out = reconstructor._sealed_job_shape(None)
     checks = reconstructor.default_checks(rows) if checks is None else checks
@@ -1031,7 +1032,7 @@ def _reveal_sealed_with_checks(name: str, aggregation: Aggregation, mask_job, re
     # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the masked output, the
     # combined mask and the output
     cap = max(n_out, 1)
-    words = (4 if max_errors is None else 16) + rows
+    words = kind.HEAD + rows
     d_buf = DeviceBuffer(2 + words + 3 * cap).zero()
     d_masked, d_mask, d_out = (d_buf.at(2 + words + i * cap) for i in range(3))
     held = []
@@ -1039,18 +1040,13 @@ def _reveal_sealed_with_checks(name: str, aggregation: Aggregation, mask_job, re
         held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
         combiner.finish_dev(d_mask, n_out)
     held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks))
-    if max_errors is None:
-        reconstructor.finish_checked_dev(d_masked, n_out, d_buf.at(2), correct)
-    else:
-        reconstructor.finish_decoded_dev(d_masked, n_out, d_buf.at(2), max_errors, correct)
+    reconstructor._finish_with_checks(kind, d_masked, n_out, d_buf.at(2), max_errors, correct)
     unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
     back = d_buf.to_numpy()
     del held
     _raise_sealed_status(int(back[0]) | int(back[1]))
     first = 2 + words + 2 * cap
-    report = back[2:2 + words].view(np.uint64).tolist()
-    return (RecipientOutput(a.modulus, back[first:first + n_out].copy()),
-            RevealCheck.from_words(report) if max_errors is None else RevealDecode.from_words(report))
+    return RecipientOutput(a.modulus, back[first:first + n_out].copy()), kind.from_words(back[2:2 + words].view(np.uint64).tolist())
 
 
 # ---- share-vector wire codec -------------------------------------------------------------

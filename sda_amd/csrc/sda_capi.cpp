@@ -1842,6 +1842,31 @@ static int prepare_R(sda_secret_reconstructor* r, const size_t* indices, size_t 
     return SDA_OK;
 }
 
+// batched.rs:84 indexes every share vector by the batch: the refusal of a short one - `which` is "" for a device row length
+static int fail_short_row(const char* which) {
+    return fail(SDA_ERR_ASSERTION, "share vector %sshorter than the number of batches (index out of bounds, batched.rs:84)", which);
+}
+static int fail_short_host_row(size_t i) {
+    char which[24];
+    snprintf(which, sizeof which, "%zu ", i);
+    return fail_short_row(which);
+}
+static int fail_not_enough_shares() { return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct"); }   // packed_shamir.rs:75
+static int fail_policy(int policy) { return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy); }
+static int fail_additive_checked() { return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check"); }
+static bool policy_known(int policy) { return policy == SDA_CHECK_REPORT || policy == SDA_CHECK_CORRECT; }
+
+// packed host rows to the device: d_out for the secrets, and `batches` values of every row in d_shares at the returned stride,
+// which is even so that every row starts 16-byte aligned
+static int stage_packed_rows(sda_secret_reconstructor* r, const int64_t* const* rows, size_t n_rows, size_t batches, size_t* stride) {
+    *stride = batches + (batches & 1);
+    SDA_TRY(r->d_shares.reserve(n_rows * *stride * 8));
+    SDA_TRY(r->d_out.reserve(r->dimension * 8));
+    for (size_t i = 0; i < n_rows && batches; ++i)
+        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * *stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
+    return SDA_OK;
+}
+
 extern "C" int sda_secret_reconstructor_reconstruct_dev(sda_secret_reconstructor_t* r, const size_t* indices,
                                                         size_t n_rows, const int64_t* d_shares, size_t row_len,
                                                         size_t row_stride, int64_t* d_out, size_t out_cap,
@@ -1859,11 +1884,11 @@ extern "C" int sda_secret_reconstructor_reconstruct_dev(sda_secret_reconstructor
         *out_len = row_len;
         return SDA_OK;
     }
-    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");   // packed_shamir.rs:75
+    if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
     if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
     const size_t batches = (r->dimension + r->k - 1) / r->k;                 // batched.rs:77
     if (batches == 0) return SDA_OK;
-    if (row_len < batches) return fail(SDA_ERR_ASSERTION, "share vector shorter than the number of batches (index out of bounds, batched.rs:84)");
+    if (row_len < batches) return fail_short_row("");
     if (!d_shares || !d_out || out_cap < r->dimension) return fail(SDA_ERR_INVALID_ARGUMENT, "bad device buffers");
     if (n_rows > 0xFFFFFFFFull) return fail(SDA_ERR_UNSUPPORTED, "too many rows");
     SDA_TRY(prepare_R(r, indices, n_rows, s));
@@ -1894,19 +1919,15 @@ extern "C" int sda_secret_reconstructor_reconstruct(sda_secret_reconstructor_t* 
         *out_len = dimension;
         return SDA_OK;
     }
-    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
+    if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
     const size_t batches = (r->dimension + r->k - 1) / r->k;
     if (batches == 0) return SDA_OK;
     for (size_t i = 0; i < n_rows; ++i)
-        if (row_lens[i] < batches) return fail(SDA_ERR_ASSERTION, "share vector %zu shorter than the number of batches (index out of bounds, batched.rs:84)", i);
+        if (row_lens[i] < batches) return fail_short_host_row(i);
     if (!out || out_cap < r->dimension) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
     SDA_TRY(r->ctx.use());
-    const size_t stride = batches + (batches & 1);
-    SDA_TRY(r->d_shares.reserve(n_rows * stride * 8));
-    SDA_TRY(r->d_out.reserve(r->dimension * 8));
-    for (size_t i = 0; i < n_rows; ++i)
-        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
-    size_t n_out = 0;
+    size_t stride = 0, n_out = 0;
+    SDA_TRY(stage_packed_rows(r, rows, n_rows, batches, &stride));
     SDA_TRY(sda_secret_reconstructor_reconstruct_dev(r, indices, n_rows, r->d_shares.as<int64_t>(), batches, stride,
                                                      r->d_out.as<int64_t>(), r->dimension, &n_out, nullptr));
     HIP_TRY(hipMemcpyAsync(out, r->d_out.p, n_out * 8, hipMemcpyDeviceToHost, r->ctx.stream));
@@ -1918,18 +1939,30 @@ extern "C" int sda_secret_reconstructor_reconstruct(sda_secret_reconstructor_t* 
 // ---- reconstruct() as a streaming job on the device (receive.rs:120-146 with the clerking results in HBM) ----------------
 // Packed: secret[b k + s] = sum over positions i of R[s][i] * share_i[b] mod q, a weighted clerk sum; the matrix is fixed once
 // the index set is declared, so a row is folded in as soon as it lands.  Additive: the plain clerk sum (additive.rs:55-73).
+
+// what a job's begin refuses of its rows; the packed checks in the order of reconstruct_dev's
+static int check_packed_job(const sda_secret_reconstructor* r, const size_t* indices, size_t n_rows, size_t row_len) {
+    if (!r->additive) {
+        if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
+        if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
+        if (row_len < (r->dimension + r->k - 1) / r->k) return fail_short_row("");                // batched.rs:77 batches
+    }
+    if (n_rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows");              // the bound the 128-bit sums rest on
+    return SDA_OK;
+}
+// the last step of a begin: the job is in flight, no position fed, `checks` parity columns behind the secrets (0: a plain job)
+static void job_commit(sda_secret_reconstructor* r, size_t n_rows, size_t row_len, size_t n_out, uint32_t checks) {
+    r->job_seen.assign(n_rows, 0);
+    r->job_rows = n_rows; r->job_row_len = row_len; r->job_fed = 0; r->job_out = n_out;
+    r->job_checks = checks;
+    r->job_begun = true;
+}
+
 extern "C" int sda_secret_reconstructor_begin_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows,
                                                   size_t row_len, void* stream) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
-    size_t n_out = row_len;
-    if (!r->additive) {
-        if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");   // packed_shamir.rs:75
-        if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
-        const size_t batches = (r->dimension + r->k - 1) / r->k;             // batched.rs:77
-        if (row_len < batches) return fail(SDA_ERR_ASSERTION, "share vector shorter than the number of batches (index out of bounds, batched.rs:84)");
-        n_out = batches * r->k;
-    }
-    if (n_rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows");              // the bound the 128-bit sums rest on
+    SDA_TRY(check_packed_job(r, indices, n_rows, row_len));
+    const size_t n_out = r->additive ? row_len : (r->dimension + r->k - 1) / r->k * r->k;    // whole batches
     SDA_TRY(r->ctx.use());
     hipStream_t s = r->ctx.pick(stream);
     if (!r->additive) SDA_TRY(prepare_R(r, indices, n_rows, s));            // colliding indices are refused here
@@ -1942,9 +1975,7 @@ extern "C" int sda_secret_reconstructor_begin_dev(sda_secret_reconstructor_t* r,
     r->job_acc.rust_signed = r->acc.rust_signed;                             // the value mode is read here
     r->job_acc.q = r->acc.q;
     SDA_TRY(r->job_acc.reset(n_out, s));
-    r->job_seen.assign(n_rows, 0);
-    r->job_rows = n_rows; r->job_row_len = row_len; r->job_fed = 0; r->job_out = r->additive ? row_len : r->dimension;
-    r->job_begun = true;
+    job_commit(r, n_rows, row_len, r->additive ? row_len : r->dimension, 0);
     return SDA_OK;
 }
 
@@ -2028,16 +2059,14 @@ extern "C" int sda_secret_reconstructor_finish_dev(sda_secret_reconstructor_t* r
 // width at run time - sum the syndromes next to the secrets in the one pass over the rows.  One faulty position c with error e:
 // S_d = u_c x_c^d e, and the all-rows reconstruction is off by R[s][c] e = (R[s][c] / u_c) S_0: the correction table.
 extern "C" size_t sda_reconstruct_report_words(size_t n_rows) { return 4 + n_rows; }
+extern "C" size_t sda_reconstruct_decode_report_words(size_t n_rows) { return 16 + n_rows; }   // the decoding finish's, below
 
 extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstructor_t* r, const size_t* indices, size_t n_rows,
                                                           size_t row_len, unsigned checks, void* stream) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
-    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
-    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");       // packed_shamir.rs:75
-    if (!indices) return fail(SDA_ERR_INVALID_ARGUMENT, "indices is NULL");
+    if (r->additive) return fail_additive_checked();
+    SDA_TRY(check_packed_job(r, indices, n_rows, row_len));
     const size_t batches = (r->dimension + r->k - 1) / r->k;                 // batched.rs:77
-    if (row_len < batches) return fail(SDA_ERR_ASSERTION, "share vector shorter than the number of batches (index out of bounds, batched.rs:84)");
-    if (n_rows > 65535) return fail(SDA_ERR_UNSUPPORTED, "at most 65535 rows");
     const size_t surplus = n_rows - ((size_t)r->t + r->k);
     if (checks == 0 || checks > SDA_RECONSTRUCT_MAX_CHECKS || checks > surplus)
         return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u: 1 .. min(%d, n_rows - (t + k) = %zu) parity checks are possible", checks,
@@ -2081,134 +2110,104 @@ extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstruct
     const hipError_t se = hipStreamSynchronize(s);                           // always: the tables are local vectors
     if (ce != hipSuccess || se != hipSuccess)
         return fail(SDA_ERR_HIP, "uploading the checked job's tables failed: %s", hipGetErrorString(ce != hipSuccess ? ce : se));
-    r->job_seen.assign(n_rows, 0);
-    r->job_rows = n_rows; r->job_row_len = row_len; r->job_fed = 0; r->job_out = r->dimension;
-    r->job_checks = checks;
-    r->job_begun = true;
+    job_commit(r, n_rows, row_len, r->dimension, checks);
     return SDA_OK;
 }
 
-extern "C" int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
-                                                           uint64_t* d_report, void* stream) {
+// The end of a checked job, one body for both finishes: the locating one (report [4 + rows], one head word at 2^64 - 1) or, with
+// `decode`, the decoding one with max_errors, 0 = checks / 2 (report [16 + rows], two such words).  A refused call leaves the
+// job as it was.
+static int finish_with_checks(sda_secret_reconstructor* r, bool decode, unsigned max_errors, int policy, int64_t* d_out, size_t out_cap,
+                              uint64_t* d_report, void* stream) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
     if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
     if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
-    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
+    if (decode && r->job_checks < 2) return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
+    if (decode && max_errors > r->job_checks / 2)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
+    if (!policy_known(policy)) return fail_policy(policy);
     if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
     if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
     if (!d_report) return fail(SDA_ERR_INVALID_ARGUMENT, "d_report is NULL");
     SDA_TRY(r->ctx.use());
     hipStream_t s = r->ctx.pick(stream);
-    HIP_TRY(hipMemsetAsync(d_report, 0, sda_reconstruct_report_words(r->job_rows) * 8, s));
-    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, 8, s));                       // no bad batch yet
+    const size_t words = decode ? sda_reconstruct_decode_report_words(r->job_rows) : sda_reconstruct_report_words(r->job_rows);
+    HIP_TRY(hipMemsetAsync(d_report, 0, words * 8, s));
+    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, decode ? 16 : 8, s));         // no bad batch and, decoding, no undecoded batch yet
     const size_t batches = (r->dimension + r->k - 1) / r->k;
-    HIP_TRY(launch_reveal_check_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                       r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows, policy == SDA_CHECK_CORRECT,
-                                       batches, r->dimension, r->mod, r->mont, d_out, d_report, s));
-    NOTE_CALL_KERNELS("reveal_check_finish_kernel");
+    if (decode)
+        HIP_TRY(launch_reveal_decode_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                            r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows,
+                                            max_errors ? max_errors : r->job_checks / 2, policy == SDA_CHECK_CORRECT, batches, r->dimension,
+                                            r->mod, r->mont, d_out, d_report, s));
+    else
+        HIP_TRY(launch_reveal_check_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                           r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows, policy == SDA_CHECK_CORRECT,
+                                           batches, r->dimension, r->mod, r->mont, d_out, d_report, s));
+    NOTE_CALL_KERNELS("%s", decode ? "reveal_decode_finish_kernel" : "reveal_check_finish_kernel");
     r->job_begun = false;
     r->job_checks = 0;
     return SDA_OK;
+}
+
+// reconstruct_checked / reconstruct_decoded: host rows through one checked job, the secrets and the report back to the host
+static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* indices, const int64_t* const* rows, const size_t* row_lens,
+                                   size_t n_rows, unsigned checks, bool decode, unsigned max_errors, int policy, int64_t* out,
+                                   size_t out_cap, size_t* out_len, uint64_t* report) {
+    if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_len = 0;
+    if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
+    if (r->additive) return fail_additive_checked();
+    if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
+    if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
+    if (!policy_known(policy)) return fail_policy(policy);
+    if (decode && (checks < 2 || max_errors > checks / 2))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: decoding takes at least 2 checks and at most checks / 2 positions", checks, max_errors);
+    const size_t batches = (r->dimension + r->k - 1) / r->k;
+    for (size_t i = 0; i < n_rows; ++i)
+        if (row_lens[i] < batches) return fail_short_host_row(i);
+    if (batches > 0 && (!out || out_cap < r->dimension)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
+    SDA_TRY(r->ctx.use());
+    const size_t words = decode ? sda_reconstruct_decode_report_words(n_rows) : sda_reconstruct_report_words(n_rows);
+    size_t stride = 0;
+    SDA_TRY(r->d_report.reserve(words * 8));
+    SDA_TRY(stage_packed_rows(r, rows, n_rows, batches, &stride));
+    SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
+    SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
+    SDA_TRY(finish_with_checks(r, decode, max_errors, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
+    if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
+    SDA_TRY(r->ctx.sync());
+    *out_len = r->dimension;
+    return SDA_OK;
+}
+
+extern "C" int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
+                                                           uint64_t* d_report, void* stream) {
+    return finish_with_checks(r, false, 0, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
                                                             uint64_t* report) {
-    if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out_len = 0;
-    if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
-    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
-    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
-    if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
-    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
-    const size_t batches = (r->dimension + r->k - 1) / r->k;
-    for (size_t i = 0; i < n_rows; ++i)
-        if (row_lens[i] < batches) return fail(SDA_ERR_ASSERTION, "share vector %zu shorter than the number of batches (index out of bounds, batched.rs:84)", i);
-    if (batches > 0 && (!out || out_cap < r->dimension)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
-    SDA_TRY(r->ctx.use());
-    const size_t stride = batches + (batches & 1), words = sda_reconstruct_report_words(n_rows);
-    SDA_TRY(r->d_shares.reserve(n_rows * stride * 8));
-    SDA_TRY(r->d_out.reserve(r->dimension * 8));
-    SDA_TRY(r->d_report.reserve(words * 8));
-    for (size_t i = 0; i < n_rows && batches; ++i)
-        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
-    SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
-    SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
-    SDA_TRY(sda_secret_reconstructor_finish_checked_dev(r, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
-    if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
-    HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
-    SDA_TRY(r->ctx.sync());
-    *out_len = r->dimension;
-    return SDA_OK;
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, false, 0, policy, out, out_cap, out_len, report);
 }
 
 // ---- the decoding finish: up to floor(checks / 2) faulty positions per batch, from the same syndromes ---------------------------
 // With errors e_i on a set E the syndromes are the power sums S_d = sum_{i in E} (u_i e_i) x_i^d: a Reed-Solomon decoding problem
 // whose solution with |E| <= checks / 2 is unique.  The kernel solves it per batch (reveal_decode.hpp); the tables are begin_checked_dev's.
-extern "C" size_t sda_reconstruct_decode_report_words(size_t n_rows) { return 16 + n_rows; }
-
 extern "C" int sda_secret_reconstructor_finish_decoded_dev(sda_secret_reconstructor_t* r, unsigned max_errors, int policy, int64_t* d_out,
                                                            size_t out_cap, uint64_t* d_report, void* stream) {
-    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
-    if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
-    if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
-    if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
-    if (r->job_checks < 2) return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
-    if (max_errors > r->job_checks / 2)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
-    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
-    if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
-    if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
-    if (!d_report) return fail(SDA_ERR_INVALID_ARGUMENT, "d_report is NULL");
-    SDA_TRY(r->ctx.use());
-    hipStream_t s = r->ctx.pick(stream);
-    HIP_TRY(hipMemsetAsync(d_report, 0, sda_reconstruct_decode_report_words(r->job_rows) * 8, s));
-    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, 16, s));                      // no bad batch, no undecoded batch yet
-    const size_t batches = (r->dimension + r->k - 1) / r->k;
-    HIP_TRY(launch_reveal_decode_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                        r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows,
-                                        max_errors ? max_errors : r->job_checks / 2, policy == SDA_CHECK_CORRECT, batches, r->dimension,
-                                        r->mod, r->mont, d_out, d_report, s));
-    NOTE_CALL_KERNELS("reveal_decode_finish_kernel");
-    r->job_begun = false;
-    r->job_checks = 0;
-    return SDA_OK;
+    return finish_with_checks(r, true, max_errors, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, unsigned max_errors, int policy, int64_t* out,
                                                             size_t out_cap, size_t* out_len, uint64_t* report) {
-    if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out_len = 0;
-    if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
-    if (r->additive) return fail(SDA_ERR_UNSUPPORTED, "additive sharing has no redundancy to check");
-    if (n_rows < (size_t)r->t + r->k) return fail(SDA_ERR_NOT_ENOUGH_SHARES, "Not enough shares to reconstruct");
-    if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
-    if (policy != SDA_CHECK_REPORT && policy != SDA_CHECK_CORRECT) return fail(SDA_ERR_INVALID_ARGUMENT, "unknown check policy %d", policy);
-    if (checks < 2 || max_errors > checks / 2)
-        return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: decoding takes at least 2 checks and at most checks / 2 positions", checks, max_errors);
-    const size_t batches = (r->dimension + r->k - 1) / r->k;
-    for (size_t i = 0; i < n_rows; ++i)
-        if (row_lens[i] < batches) return fail(SDA_ERR_ASSERTION, "share vector %zu shorter than the number of batches (index out of bounds, batched.rs:84)", i);
-    if (batches > 0 && (!out || out_cap < r->dimension)) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
-    SDA_TRY(r->ctx.use());
-    const size_t stride = batches + (batches & 1), words = sda_reconstruct_decode_report_words(n_rows);
-    SDA_TRY(r->d_shares.reserve(n_rows * stride * 8));
-    SDA_TRY(r->d_out.reserve(r->dimension * 8));
-    SDA_TRY(r->d_report.reserve(words * 8));
-    for (size_t i = 0; i < n_rows && batches; ++i)
-        HIP_TRY(hipMemcpyAsync(r->d_shares.as<int64_t>() + i * stride, rows[i], batches * 8, hipMemcpyHostToDevice, r->ctx.stream));
-    SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
-    SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
-    SDA_TRY(sda_secret_reconstructor_finish_decoded_dev(r, max_errors, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
-    if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
-    HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
-    SDA_TRY(r->ctx.sync());
-    *out_len = r->dimension;
-    return SDA_OK;
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, true, max_errors, policy, out, out_cap, out_len, report);
 }
 
 // =================================================================================================

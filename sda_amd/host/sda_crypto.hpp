@@ -353,18 +353,13 @@ struct SecretReconstructor {
     void set_value_mode(int mode) { detail::check(sda_secret_reconstructor_set_value_mode(h, mode)); }
     SecretReconstructor(const SecretReconstructor&) = delete;
     std::vector<Secret> reconstruct(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares) const {
-        std::vector<size_t> idx(indexed_shares.size()), lens(indexed_shares.size());
-        std::vector<const int64_t*> ptrs(indexed_shares.size());
+        HostCall c(indexed_shares, 0, 0);
         size_t cap = dimension;
-        for (size_t i = 0; i < indexed_shares.size(); ++i) {
-            idx[i] = indexed_shares[i].first; ptrs[i] = indexed_shares[i].second.data(); lens[i] = indexed_shares[i].second.size();
-            if (lens[i] > cap) cap = lens[i];
-        }
-        std::vector<Secret> out(cap);
-        size_t n_out = 0;
-        detail::check(sda_secret_reconstructor_reconstruct(h, idx.data(), ptrs.data(), lens.data(), idx.size(), out.data(), cap, &n_out));
-        out.resize(n_out);
-        return out;
+        for (size_t len : c.lens) cap = len > cap ? len : cap;
+        c.out.resize(cap);
+        detail::check(sda_secret_reconstructor_reconstruct(h, c.idx.data(), c.ptrs.data(), c.lens.data(), c.idx.size(), c.out.data(), cap, &c.n_out));
+        c.out.resize(c.n_out);
+        return std::move(c.out);
     }
     // the same as a streaming job on device-resident rows (receive.rs:120-146); no update synchronises the stream.  indices[i] is
     // the clerk index of position i (Additive: may be empty); a position is fed once, in any order, by either update form
@@ -391,6 +386,12 @@ struct SecretReconstructor {
         uint64_t bad = 0, located = 0, corrected = 0, first_bad = ~0ull;     // first_bad: 2^64 - 1 = none
         std::vector<uint64_t> blame;                                          // per position of the index set
         bool clean() const { return bad == 0; }
+        static RevealCheck from_words(const std::vector<uint64_t>& w) {
+            RevealCheck c;
+            c.bad = w[0]; c.located = w[1]; c.corrected = w[2]; c.first_bad = w[3];
+            c.blame.assign(w.begin() + 4, w.end());
+            return c;
+        }
     };
     void begin_checked_dev(const std::vector<size_t>& indices, size_t n_rows, size_t row_len, unsigned checks, void* stream = nullptr) {
         if (indices.size() != n_rows) detail::check(SDA_ERR_INVALID_ARGUMENT);
@@ -403,23 +404,12 @@ struct SecretReconstructor {
     }
     std::pair<std::vector<Secret>, RevealCheck> reconstruct_checked(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares,
                                                                     unsigned checks, bool correct = false) const {
-        const size_t n = indexed_shares.size();
-        std::vector<size_t> idx(n), lens(n);
-        std::vector<const int64_t*> ptrs(n);
-        for (size_t i = 0; i < n; ++i) {
-            idx[i] = indexed_shares[i].first; ptrs[i] = indexed_shares[i].second.data(); lens[i] = indexed_shares[i].second.size();
-        }
-        std::vector<Secret> out(dimension ? dimension : 1);
-        std::vector<uint64_t> words(sda_reconstruct_report_words(n));
-        size_t n_out = 0;
-        detail::check(sda_secret_reconstructor_reconstruct_checked(h, idx.data(), ptrs.data(), lens.data(), n, checks,
-                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, out.data(), dimension,
-                                                                   &n_out, words.data()));
-        out.resize(n_out);
-        RevealCheck c;
-        c.bad = words[0]; c.located = words[1]; c.corrected = words[2]; c.first_bad = words[3];
-        c.blame.assign(words.begin() + 4, words.end());
-        return {std::move(out), std::move(c)};
+        HostCall c(indexed_shares, dimension, sda_reconstruct_report_words(indexed_shares.size()));
+        detail::check(sda_secret_reconstructor_reconstruct_checked(h, c.idx.data(), c.ptrs.data(), c.lens.data(), c.idx.size(), checks,
+                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, c.out.data(), dimension,
+                                                                   &c.n_out, c.words.data()));
+        c.out.resize(c.n_out);
+        return {std::move(c.out), RevealCheck::from_words(c.words)};
     }
     // the decoding finish of a checked job: up to max_errors (0: checks / 2) disagreeing positions per batch are named and, on
     // request, repaired (sda_hip.h: the report words, what a cap guarantees)
@@ -444,21 +434,27 @@ struct SecretReconstructor {
     }
     std::pair<std::vector<Secret>, RevealDecode> reconstruct_decoded(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares,
                                                                      unsigned checks, unsigned max_errors = 0, bool correct = false) const {
-        const size_t n = indexed_shares.size();
-        std::vector<size_t> idx(n), lens(n);
-        std::vector<const int64_t*> ptrs(n);
-        for (size_t i = 0; i < n; ++i) {
-            idx[i] = indexed_shares[i].first; ptrs[i] = indexed_shares[i].second.data(); lens[i] = indexed_shares[i].second.size();
-        }
-        std::vector<Secret> out(dimension ? dimension : 1);
-        std::vector<uint64_t> words(sda_reconstruct_decode_report_words(n));
-        size_t n_out = 0;
-        detail::check(sda_secret_reconstructor_reconstruct_decoded(h, idx.data(), ptrs.data(), lens.data(), n, checks, max_errors,
-                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, out.data(), dimension,
-                                                                   &n_out, words.data()));
-        out.resize(n_out);
-        return {std::move(out), RevealDecode::from_words(words)};
+        HostCall c(indexed_shares, dimension, sda_reconstruct_decode_report_words(indexed_shares.size()));
+        detail::check(sda_secret_reconstructor_reconstruct_decoded(h, c.idx.data(), c.ptrs.data(), c.lens.data(), c.idx.size(), checks, max_errors,
+                                                                   correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, c.out.data(), dimension,
+                                                                   &c.n_out, c.words.data()));
+        c.out.resize(c.n_out);
+        return {std::move(c.out), RevealDecode::from_words(c.words)};
     }
+
+private:
+    // the arguments of a host reconstruct call: indexed_shares unpacked, the output and the report sized
+    struct HostCall {
+        std::vector<size_t> idx, lens;
+        std::vector<const int64_t*> ptrs;
+        std::vector<Secret> out;
+        std::vector<uint64_t> words;
+        size_t n_out = 0;
+        HostCall(const std::vector<std::pair<size_t, std::vector<Share>>>& s, size_t out_cap, size_t n_words)
+            : idx(s.size()), lens(s.size()), ptrs(s.size()), out(out_cap ? out_cap : 1), words(n_words) {
+            for (size_t i = 0; i < s.size(); ++i) { idx[i] = s[i].first; ptrs[i] = s[i].second.data(); lens[i] = s[i].second.size(); }
+        }
+    };
 };
 
 // ---- masking traits -----------------------------------------------------------------------------

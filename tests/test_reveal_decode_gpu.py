@@ -142,6 +142,87 @@ def test_refusals_leave_the_job_usable(gpu):
     assert e.value.code == capi.ERR_UNSUPPORTED
 
 
+def test_refusal_order_is_the_parents(gpu):
+    """calls that carry two or three faults at once: which one is reported is part of the interface.  Both device finishes refuse
+    in the order  no job > plain job > unfed positions > (decoded: one check > max_errors) > policy > d_out > out_cap > d_report,
+    the host forms in the order  additive > rows short of t + k > report > policy > (decoded: checks, max_errors) > a short row >
+    out.  Every refused call leaves the job to finish with the model's output."""
+    import ctypes as C
+    from sda_amd import capi, crypto
+    from sda_amd.device import DeviceBuffer
+    case, b = dc.BY_NAME[dc.E2E], dc.build(dc.E2E)
+    pk, sk = _keys(49)
+    L, pos = b.row_len, len(case.indices)
+    assert pos == 8 and case.checks == 4
+    d_out, d_report = DeviceBuffer(case.dim + 1), DeviceBuffer(dc.HEAD + pos)
+    rec = crypto.SecretReconstructor(scheme_of(case), case.dim)
+    f = Feeder(rec, b.rows, None, pk, sk)
+    checked = lambda policy, out, cap, report, max_errors=None: gpu.sda_secret_reconstructor_finish_checked_dev(
+        rec._h, policy, out, cap, report, None)
+    decoded = lambda policy, out, cap, report, max_errors=0: gpu.sda_secret_reconstructor_finish_decoded_dev(
+        rec._h, max_errors, policy, out, cap, report, None)
+
+    def refused(status, code, word):
+        text = gpu.sda_last_error().decode()
+        assert status == code and word in text, (status, text, code, word)
+
+    BAD_POLICY = 7
+    # a plain job + NULL d_out: the kind of the job comes first
+    rec.begin_dev(case.indices, pos, L)
+    f.plain(0, pos)
+    for fin in (checked, decoded):
+        refused(fin(capi.CHECK_CORRECT, None, case.dim, d_report.ptr), capi.ERR_STATE, "begin_dev")
+    rec.finish_dev(d_out.ptr, case.dim)
+    assert np.array_equal(d_out.to_numpy()[:case.dim], dc.model_finish(case, b.rows, dc.REPORT).out)
+
+    # the checked job of four checks, half fed
+    rec.begin_checked_dev(case.indices, pos, L, case.checks)
+    f.plain(0, 4)
+    for fin in (checked, decoded):
+        refused(fin(BAD_POLICY, d_out.ptr, case.dim, d_report.ptr), capi.ERR_STATE, "not fed")                  # unfed + policy
+    refused(decoded(capi.CHECK_CORRECT, d_out.ptr, case.dim, d_report.ptr, max_errors=3), capi.ERR_STATE, "not fed")   # unfed + max_errors
+    f.plain(4, pos - 4)
+    for fin in (checked, decoded):
+        refused(fin(BAD_POLICY, d_out.ptr, case.dim - 1, d_report.ptr), capi.ERR_INVALID_ARGUMENT, "policy")    # policy + short out_cap
+        refused(fin(capi.CHECK_CORRECT, d_out.ptr, case.dim - 1, None), capi.ERR_INVALID_ARGUMENT, "too small")  # short out_cap + NULL report
+    refused(decoded(BAD_POLICY, d_out.ptr, case.dim, d_report.ptr, max_errors=3), capi.ERR_INVALID_ARGUMENT, "max_errors")
+    out, report = finish_decoded(rec, case, True)
+    want = dc.model_finish(case, b.rows, dc.CORRECT)
+    assert report == want.report and np.array_equal(out, want.out)
+
+    # a job of one check + an unknown policy: the decoding finish names the check count
+    one = case._replace(checks=1)
+    rec.begin_checked_dev(case.indices, pos, L, 1)
+    f.plain(0, pos)
+    refused(decoded(BAD_POLICY, d_out.ptr, case.dim, d_report.ptr), capi.ERR_INVALID_ARGUMENT, "one check")
+    refused(checked(BAD_POLICY, d_out.ptr, case.dim - 1, d_report.ptr), capi.ERR_INVALID_ARGUMENT, "policy")
+    out, report = finish_checked(rec, one, True)
+    old = vc.model_finish(one, b.rows, vc.CORRECT)
+    assert report == old.report and np.array_equal(out, old.out)
+
+    # the host forms
+    def host(r, which, rows, checks, policy, with_report, max_errors=0):
+        arrs = [np.ascontiguousarray(x, dtype=np.int64) for x in rows]
+        idx = (C.c_size_t * len(arrs))(*case.indices[:len(arrs)])
+        ptrs = (capi.c_i64p * len(arrs))(*[a.ctypes.data_as(capi.c_i64p) for a in arrs])
+        lens = (C.c_size_t * len(arrs))(*[a.size for a in arrs])
+        out, n_out = np.empty(case.dim, dtype=np.int64), C.c_size_t()
+        words = (C.c_uint64 * (dc.HEAD + len(arrs)))() if with_report else None
+        tail = (policy, out.ctypes.data_as(capi.c_i64p), case.dim, C.byref(n_out), words)
+        if which == "checked":
+            return gpu.sda_secret_reconstructor_reconstruct_checked(r._h, idx, ptrs, lens, len(arrs), checks, *tail)
+        return gpu.sda_secret_reconstructor_reconstruct_decoded(r._h, idx, ptrs, lens, len(arrs), checks, max_errors, *tail)
+
+    short = [r for r in b.rows[:-1]] + [b.rows[-1][:dc.batches(case) - 1]]
+    add = crypto.SecretReconstructor(crypto.Additive(3, vc.SCHEMES[case.scheme][0]), 10)
+    for which in ("checked", "decoded"):
+        refused(host(add, which, np.zeros((3, 10), dtype=np.int64), 2, capi.CHECK_REPORT, False), capi.ERR_UNSUPPORTED, "additive")
+        refused(host(rec, which, b.rows, 4, BAD_POLICY, False), capi.ERR_INVALID_ARGUMENT, "report is NULL")
+        refused(host(rec, which, short, 4, BAD_POLICY, True), capi.ERR_INVALID_ARGUMENT, "policy")
+    refused(host(rec, "decoded", short, 1, capi.CHECK_REPORT, True), capi.ERR_INVALID_ARGUMENT, "at least 2 checks")
+    refused(host(rec, "checked", short, 1, capi.CHECK_REPORT, True), capi.ERR_ASSERTION, "share vector 7 shorter")
+
+
 # ---- 3. two tampered boxes of eight --------------------------------------------------------------------------------------------------
 def _tampered_job(b, pk, liars):
     from oracle import coracle, sealedbox_oracle as so
