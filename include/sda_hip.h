@@ -514,6 +514,61 @@ int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, 
                                                  size_t* out_len,
                                                  uint64_t* report /* host, sda_reconstruct_decode_report_words(n_rows) */);
 
+/* The ERASURE finish of a checked job: a third way to end it, for positions the caller already knows to be unreliable - first of
+ * all the rows sda_secret_reconstructor_update_sealed_rows_dev refused (d_ok[r] = 0, *d_status |= 16).  A position the decoder
+ * must FIND costs two of the job's checks, a position it is TOLD costs one.  THE REFERENCE'S RULE STANDS: the reference fails the
+ * whole reveal on a refused box (sodium.rs:78-80), and *d_status is the caller's to read; this call is the deliberate alternative
+ * for a caller who prefers the other clerks' answer to none, not a replacement of that rule.
+ * sda_secret_unmasker_unmask_jobs_dev keeps refusing checked jobs.
+ *
+ *   The definition.  F = the f erased positions, Gamma(z) = prod_{j in F} (z - x_j) = sum_m gamma_m z^m, c = the job's checks.
+ *   The MODIFIED SYNDROMES are T_j = sum_m gamma_m S_{j+m}, j = 0 .. c - f - 1.  If position i added v_i where the true share
+ *   differs by e_i, and Y_i = u_i e_i, then T_j = sum_{i not in F} (Y_i Gamma(x_i)) x_i^j: the erased positions drop out WHATEVER
+ *   THEY ADDED - a row refused, a row fed with garbage and a row fed correctly give the same T.  With e' = min(cap, floor((c - f)
+ *   / 2)), cap = max_errors or unlimited when 0: a batch is CONSISTENT when every T_j = 0 and BAD otherwise; a bad batch is DECODED
+ *   WITH nu POSITIONS (1 <= nu <= e') when nu distinct NON-ERASED positions and non-zero Z_i reproduce all c - f modified
+ *   syndromes (unique when it exists: Vandermonde), and then Y_i = Z_i / Gamma(x_i) on those positions E.  For a consistent or
+ *   decoded batch the erased magnitudes are the unique solution of sum_{j in F} Y_j x_j^d = S_d - sum_{i in E} Y_i x_i^d,
+ *   d = 0 .. f - 1.
+ *
+ *   finish_erasures_dev : ends a job begun by begin_checked_dev, like finish_decoded_dev, and refuses what that call refuses, in
+ *               the same order with the same texts and codes - except that a job with checks == 1 is accepted (one erasure is
+ *               repairable, errors are only detected); max_errors is still validated against floor(checks / 2).  An unfed
+ *               position stays SDA_ERR_STATE: to mark a clerk who never delivered, feed the position (with anything) and flag it,
+ *               or drop it before begin.  Additive and plain jobs are refused as for finish_decoded_dev.
+ *               d_ok: n_rows DEVICE words in job position order, 0 = erased, anything else = not; NULL = none.  It is the layout
+ *               the sealed updates write: pass d_ok + first_pos to each update_sealed_rows_dev and hand the same array over
+ *               unchanged.  It is read only when the kernels run: the host never learns f, and the call does not synchronise,
+ *               copies nothing to the host and allocates nothing after the first use of its scratch.  Two kernels.
+ *                 SDA_CHECK_REPORT : d_out is bit for bit finish_dev's for the same rows; the report says what would be decoded.
+ *                 SDA_CHECK_CORRECT: the k secrets of a consistent or decoded batch lose sum_{i in E u F} (R[s][i] / u_i) Y_i -
+ *                                    when at most e' non-erased rows of the batch are truly faulty, bit for bit what
+ *                                    sda_secret_reconstructor_reconstruct returns for the n_rows - f - nu other rows.  An
+ *                                    undecoded bad batch is stored as under SDA_CHECK_REPORT.
+ *               d_report: sda_reconstruct_decode_report_words(n_rows) words in finish_decoded_dev's layout - [0] bad, [1]
+ *               decoded, [2] corrected batches (decoded batches under SDA_CHECK_CORRECT: a consistent batch repaired by its
+ *               erasures alone is not counted), [3] first bad, [4] first undecoded batch, [5] the largest nu, [8 ..] batches by
+ *               nu, [16 + i] blame of the NON-ERASED position i (an erased position stays 0) - and
+ *               [6] = f,  [7] = 1 when f > checks: then nothing is decoded, d_out is finish_dev's and [0 .. 5] keep their initial
+ *               values; otherwise 0.  With d_ok == NULL or no zero word in it, d_out and the whole report are bit for bit
+ *               finish_decoded_dev's (on a job with checks >= 2).
+ *   reconstruct_erasures : the host form - reconstruct_decoded with `erased` (host, n_rows bytes, non-zero = erased; NULL = none)
+ *               after checks; checks == 1 is accepted, max_errors > floor(checks / 2) -> SDA_ERR_INVALID_ARGUMENT.
+ *
+ *   What is guaranteed per batch: f erasures with 1 .. e' errors are repaired exactly; e' + 1 .. c - f - e' errors are always
+ *   detected and stay undecoded; f = c detects nothing (the f rows are solved from the c sums, and the other rows are taken on
+ *   trust); f > c repairs nothing and says so in [7]. */
+int sda_secret_reconstructor_finish_erasures_dev(sda_secret_reconstructor_t* r,
+                                                 const uint32_t* d_ok /* device, n_rows words, 0 = erased; NULL = none */,
+                                                 unsigned max_errors, int policy, int64_t* d_out, size_t out_cap, uint64_t* d_report,
+                                                 void* stream);
+int sda_secret_reconstructor_reconstruct_erasures(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                  const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                  unsigned checks,
+                                                  const uint8_t* erased /* host, n_rows bytes, non-zero = erased; NULL = none */,
+                                                  unsigned max_errors, int policy, int64_t* out, size_t out_cap, size_t* out_len,
+                                                  uint64_t* report /* host, sda_reconstruct_decode_report_words(n_rows) */);
+
 /* =============================================================================================
  * SecretMasker / MaskCombiner / SecretUnmasker  (masking/mod.rs:9-31; impl none.rs, full.rs, chacha.rs)
  * ============================================================================================= */

@@ -232,6 +232,10 @@ SIGNATURES = {
     "sda_secret_reconstructor_finish_decoded_dev": (C.c_int, [_H, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_secret_reconstructor_reconstruct_decoded": (C.c_int, [_H, c_sizep, c_i64pp, c_sizep, C.c_size_t, C.c_uint, C.c_uint, C.c_int,
                                                                c_i64p, C.c_size_t, c_sizep, C.POINTER(C.c_uint64)]),
+    "sda_secret_reconstructor_finish_erasures_dev": (C.c_int, [_H, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                               C.c_void_p]),
+    "sda_secret_reconstructor_reconstruct_erasures": (C.c_int, [_H, c_sizep, c_i64pp, c_sizep, C.c_size_t, C.c_uint, C.c_char_p, C.c_uint,
+                                                                C.c_int, c_i64p, C.c_size_t, c_sizep, C.POINTER(C.c_uint64)]),
     "sda_comm_unique_id": (C.c_int, [c_u8p]),
     "sda_comm_init": (C.c_int, [c_u8p, C.c_int, C.c_int, _HP]),
     "sda_comm_free": (None, [_H]),

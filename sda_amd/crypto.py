@@ -601,6 +601,38 @@ class SecretReconstructor(_Handle):
         """reconstruct_checked with the decoding finish: (values, RevealDecode)"""
         return self._reconstruct_with_checks(RevealDecode, indexed_shares, checks, max_errors, correct)
 
+    # the erasure finish of a checked job: positions known to be unreliable (a refused sealed row) cost one check each, not two
+    def finish_erasures_dev(self, d_ok: int, d_out: int, out_cap: int, d_report: int, max_errors: int = 0, correct: bool = False,
+                            stream: int = 0) -> None:
+        """ends a job begun by begin_checked_dev around the erased positions: d_ok is n_rows device words, 0 = erased (what
+        update_sealed_rows_dev writes; 0: none), read by the kernels alone.  d_report: 16 + n_rows device words in
+        finish_decoded_dev's layout, [6] = the number of erased positions, [7] = 1 when there are more than checks.  Nothing
+        synchronises or reaches the host"""
+        check(self._lib.sda_secret_reconstructor_finish_erasures_dev(self._h, d_ok or None, max_errors,
+                                                                     capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, d_out or None, out_cap,
+                                                                     d_report or None, stream or None))
+
+    def reconstruct_erasures(self, indexed_shares: Sequence[Tuple[int, Sequence]], erased: Optional[Sequence] = None,
+                             checks: Optional[int] = None, max_errors: int = 0,
+                             correct: bool = False) -> Tuple[np.ndarray, "RevealDecode", int, bool]:
+        """reconstruct_decoded around the rows that `erased` flags (one truth value per row; None: none): (values, RevealDecode, the
+        number of erased rows as the device counted them, whether they were more than checks)"""
+        arrs, ptrs, lens = _rows([v for _, v in indexed_shares])
+        cidx = _index_array([i for i, _ in indexed_shares])
+        if checks is None and not isinstance(self.scheme, Additive):
+            checks = self.default_checks(len(arrs))
+        if erased is not None and len(erased) != len(arrs):
+            raise SdaError(capi.ERR_INVALID_ARGUMENT, f"{len(erased)} erasure flags for {len(arrs)} rows")
+        flags = None if erased is None else bytes(1 if e else 0 for e in erased)
+        out = np.empty(max(self.dimension, 1), dtype=np.int64)
+        report = (C.c_uint64 * (RevealDecode.HEAD + len(arrs)))()
+        n_out = C.c_size_t()
+        check(self._lib.sda_secret_reconstructor_reconstruct_erasures(
+            self._h, cidx, ptrs, lens, len(arrs), max(int(checks or 0), 0), flags, max_errors,
+            capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, _ptr(out), self.dimension, C.byref(n_out), report))
+        words = list(report)
+        return out[:n_out.value].copy(), RevealDecode.from_words(words), int(words[6]), bool(words[7])
+
     def reconstruct_sealed_job_decoded(self, blob, indices: Sequence[int], pk: bytes, sk: bytes, checks: Optional[int] = None,
                                        max_errors: int = 0, correct: bool = False) -> Tuple[np.ndarray, "RevealDecode"]:
         """reconstruct_sealed_job_checked with the decoding finish: (values, RevealDecode).  A bad box still fails the reveal
@@ -631,10 +663,10 @@ class SecretReconstructor(_Handle):
         return row_len, (row_len if additive else self.dimension)
 
     def _feed_sealed_job(self, job: "JobContainer", indices: Optional[Sequence[int]], row_len: int, pk: bytes, sk: bytes,
-                         d_status: int, checks: Optional[int] = None):
+                         d_status: int, checks: Optional[int] = None, d_ok: int = 0):
         """begin_dev (checks given: begin_checked_dev) + update_sealed_rows_dev over a parsed SDAJOBv1 SEALED job, row i from
-        clerk indices[i]; the failures of the boxes land in *d_status.  Returns what must stay alive until the job's stream work
-        is done"""
+        clerk indices[i]; the failures of the boxes land in *d_status and, with d_ok, one word per row in d_ok[].  Returns what
+        must stay alive until the job's stream work is done"""
         from .device import DeviceBytes
         L = job.layout
         if checks is None:
@@ -646,7 +678,7 @@ class SecretReconstructor(_Handle):
         d_job = DeviceBytes.from_bytes(job.blob)
         codec, box = VarintCodec(), SealedBox()
         self.update_sealed_rows_dev(codec, box, pk, sk, 0, d_job.ptr + L.payload_offset, L.slot_bytes,
-                                    d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status)
+                                    d_job.ptr + L.lengths_offset, L.rows, L.slot_bytes, d_status, d_ok)
         return d_job, codec, box
 
 
@@ -1010,6 +1042,59 @@ def reveal_sealed_decoded(aggregation: Aggregation, mask_job, result_job, indice
     A bad box still fails the reveal (sodium.rs:78-80)."""
     return _reveal_sealed_with_checks(RevealDecode, "reveal_sealed_decoded", aggregation, mask_job, result_job, indices, recipient_pk,
                                       recipient_sk, checks, max_errors, correct)
+
+
+class RevealRepair(NamedTuple):
+    """what reveal_sealed_repaired returns: the output, the report, the status word of the clerking results' sealed update (bit 16:
+    some box was refused) and the number of refused boxes as the device counted them; unrepaired: they were more than checks"""
+    output: RecipientOutput
+    decode: RevealDecode
+    status: int
+    refused: int
+    unrepaired: bool
+
+
+def reveal_sealed_repaired(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
+                           recipient_sk: bytes, checks: Optional[int] = None, max_errors: int = 0, correct: bool = True) -> RevealRepair:
+    """reveal_sealed_decoded that REPAIRS refused clerking results instead of failing on them - the deliberate alternative to the
+    reference's rule (sodium.rs:78-80), for a caller who prefers the other clerks' answer to none.  The sealed update's d_ok words
+    go to SecretReconstructor.finish_erasures_dev untouched and unread: a refused box is an erasure and costs one check, not two.
+    The status word of the clerking results is RETURNED, not raised, for its bit 16; every other failure - a bad mask box, a wrong
+    dimension, a malformed stream - fails the reveal as in reveal_sealed."""
+    from .device import DeviceBuffer
+    a = aggregation
+    sch, msch = a.committee_sharing_scheme, a.masking_scheme
+    masks, results = _parse_reveal_jobs("reveal_sealed_repaired", msch, mask_job, result_job, recipient_pk, recipient_sk)
+    if isinstance(sch, Additive):
+        raise SdaError(capi.ERR_UNSUPPORTED, "additive sharing has no redundancy to check")
+    rows = results.layout.rows
+    _check_result_indices(indices, rows, optional=False)
+    reconstructor = SecretReconstructor(sch, a.vector_dimension)
+    row_len, n_out = reconstructor._sealed_job_shape(None)
+    checks = reconstructor.default_checks(rows) if checks is None else checks
+    unmasker = SecretUnmasker(msch)
+    combiner = MaskCombiner(msch) if masks is not None else None
+    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the masked output, the
+    # combined mask, the output and the rows' ok words (two 32-bit words per entry)
+    cap = max(n_out, 1)
+    words = RevealDecode.HEAD + rows
+    d_buf = DeviceBuffer(2 + words + 3 * cap + (rows + 1) // 2).zero()
+    d_masked, d_mask, d_out, d_ok = (d_buf.at(2 + words + i * cap) for i in range(4))
+    held = []
+    if combiner is not None:
+        held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
+        combiner.finish_dev(d_mask, n_out)
+    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks, d_ok=d_ok))
+    reconstructor.finish_erasures_dev(d_ok, d_masked, n_out, d_buf.at(2), max_errors, correct)
+    unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
+    back = d_buf.to_numpy()
+    del held
+    status = int(back[1]) & 0xFFFFFFFF
+    _raise_sealed_status(int(back[0]) | (status & ~16))
+    report = back[2:2 + words].view(np.uint64).tolist()
+    first = 2 + words + 2 * cap
+    return RevealRepair(RecipientOutput(a.modulus, back[first:first + n_out].copy()), RevealDecode.from_words(report), status,
+                        int(report[6]), bool(report[7]))
 
 
 def _reveal_sealed_with_checks(kind, name: str, aggregation: Aggregation, mask_job, result_job, indices, recipient_pk: bytes,

@@ -272,6 +272,17 @@ hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* 
                                        uint32_t k, uint32_t checks, uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches,
                                        size_t dimension, const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report,
                                        hipStream_t s);
+// the ERASURE finish of the same job: d_ok [n_rows] device words, 0 = position i is erased whatever it added (nullptr: none);
+// d_table: reveal_erasure_table_words(n_rows) device words of scratch.  reveal_erasure_setup_kernel (one workgroup) compacts the
+// f erased positions and builds the per-job tables, reveal_erasure_finish_kernel decodes the modified syndromes T_j = sum_m
+// gamma_m S_{j+m}, j < checks - f, with at most min(max_errors or 8, (checks - f) / 2) non-erased positions and, under `correct`,
+// solves the erased magnitudes and subtracts the correction over both sets.  d_report as for the decoding finish, with [6] = f and
+// [7] = 1 when f > checks (then d_out is the plain fold and nothing else is reported).  checks 1 .. 16, max_errors <= checks / 2
+size_t reveal_erasure_table_words(size_t n_rows);
+hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                        const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks, uint32_t n_rows,
+                                        uint32_t max_errors, bool correct, size_t batches, size_t dimension, const ModParams& mod,
+                                        const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

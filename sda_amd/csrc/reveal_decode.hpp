@@ -11,6 +11,8 @@
 // loops, x^m B is kept shifted (one compile-time shift per step) and the syndromes rotate through S[0] - sixteen rotations bring
 // them back.  The located positions go through `pos` (LDS in the kernel).
 #pragma once
+#include <stddef.h>
+
 #include "modarith.hpp"
 
 namespace sda {
@@ -133,6 +135,145 @@ SDA_HD uint64_t decode_magnitude(const uint64_t (&C)[kDecodeErrors + 1], const u
         if ((e >> bit) & 1) inv = dec_mm(inv, den, p, pinv);
     }
     return dec_mm(num, inv, p, pinv);
+}
+
+// ---- erasures: positions the caller knows to be unreliable (sda_secret_reconstructor_finish_erasures_dev) ---------------------------
+// F = the f erased positions, Gamma(z) = prod_{j in F} (z - x_j).  The MODIFIED syndromes T_j = sum_m gamma_m S_{j+m}, j < c - f,
+// are the power sums of Z_i = Y_i Gamma(x_i) over the non-erased positions alone: the decoder above runs on T with length c - f,
+// Y_i = Z_i / Gamma(x_i), and once the located errors are taken out of S_0 .. S_{f-1} the erased magnitudes are f dot products with
+// the rows g_{j,m} / Gamma_j(x_j), Gamma_j(z) = Gamma(z) / (z - x_j).  What depends on the job and F only - the erased positions,
+// those rows and 1 / Gamma(x_i) - is built once per finish (reveal_erasure_setup_kernel) into a table of 64-bit words, all in
+// Montgomery form like xs; S, T, Y and Z are canonical, so a product of a table entry and one of them is exact after its one REDC.
+static constexpr int kEraseMax = kDecodeChecks;            // the most erased positions a job can repair
+static constexpr int kEraseCount = 0;                      // [0] f, counted in full;  [1] 1 when f > checks: nothing is repaired
+static constexpr int kEraseOver = 1;
+static constexpr int kErasePos = 2;                        // [2 + j] the j-th erased position, ascending, j < min(f, 16)
+static constexpr int kEraseRows = kErasePos + kEraseMax;   // [18 + 16 j + m] g_{j,m} / Gamma_j(x_j), j, m < f
+static constexpr int kEraseInv = kEraseRows + kEraseMax * kEraseMax;   // [274 + i] 1 / Gamma(x_i); 0 = position i is erased
+SDA_HD constexpr size_t erase_table_words(size_t n_rows) { return (size_t)kEraseInv + n_rows; }
+
+// a R -> R / a (both Montgomery form) by Fermat; 0 -> 0
+SDA_HD uint64_t dec_inv(uint64_t a, uint64_t p, uint64_t pinv) {
+    const uint64_t e = p - 2;
+    int top = 63;
+    while (top > 0 && !((e >> top) & 1)) --top;
+    uint64_t inv = a;
+    for (int bit = top - 1; bit >= 0; --bit) {
+        inv = dec_mm(inv, inv, p, pinv);
+        if ((e >> bit) & 1) inv = dec_mm(inv, a, p, pinv);
+    }
+    return inv;
+}
+
+// gam[0 .. kEraseMax]: the coefficients of Gamma (Montgomery form, 0 past f) from the f <= 16 erased positions; one = 2^64 mod p
+SDA_HD void erase_gamma(const uint64_t* xs, const uint32_t* epos, uint32_t f, uint64_t one, uint64_t p, uint64_t pinv, uint64_t* gam) {
+    for (int m = 0; m <= kEraseMax; ++m) gam[m] = 0;
+    gam[0] = one;
+    for (uint32_t j = 0; j < f; ++j) {
+        const uint64_t x = xs[epos[j]];
+        for (uint32_t m = j + 1; m >= 1; --m) gam[m] = submod(gam[m - 1], dec_mm(gam[m], x, p, pinv), p);
+        gam[0] = submod(0, dec_mm(gam[0], x, p, pinv), p);
+    }
+}
+
+// row[m] = g_{j,m} / Gamma_j(x_j), m < f, for the erased point xj (f >= 1): synthetic division of Gamma by (z - xj) from the top,
+// Horner for Gamma_j(xj) on the way down, one Fermat power
+SDA_HD void erase_solve_row(const uint64_t* gam, uint32_t f, uint64_t xj, uint64_t p, uint64_t pinv, uint64_t* row) {
+    uint64_t g = gam[f], den = g;
+    row[f - 1] = g;
+    for (uint32_t m = f - 1; m >= 1; --m) {
+        g = addmod(gam[m], dec_mm(g, xj, p, pinv), p);
+        row[m - 1] = g;
+        den = addmod(dec_mm(den, xj, p, pinv), g, p);
+    }
+    const uint64_t inv = dec_inv(den, p, pinv);
+    for (uint32_t m = 0; m < f; ++m) row[m] = dec_mm(row[m], inv, p, pinv);
+}
+
+// 1 / Gamma(x); 0 exactly when x is one of the erased points (the job's points are distinct).  Nothing erased: Gamma = 1, no power
+SDA_HD uint64_t erase_inv_gamma(const uint64_t* gam, uint32_t f, uint64_t x, uint64_t p, uint64_t pinv) {
+    if (f == 0) return gam[0];
+    uint64_t acc = gam[f];
+    for (uint32_t m = f; m >= 1; --m) acc = addmod(dec_mm(acc, x, p, pinv), gam[m - 1], p);
+    return dec_inv(acc, p, pinv);
+}
+
+// T(z) <- (z - x) T(z) read as T_j <- T_{j+1} - x T_j: one erased point folded into the syndromes, in place.  Every such step
+// costs the sequence its last valid entry - after f of them T_0 .. T_{c-f-1} are the modified syndromes, erase_keep drops the rest.
+SDA_HD void erase_fold_point(uint64_t (&T)[kDecodeChecks], uint32_t checks, uint64_t x, uint64_t p, uint64_t pinv) {
+#pragma unroll
+    for (int j = 0; j + 1 < kDecodeChecks; ++j)
+        if ((uint32_t)(j + 1) < checks) T[j] = submod(T[j + 1], dec_mm(T[j], x, p, pinv), p);
+}
+SDA_HD void erase_keep(uint64_t (&T)[kDecodeChecks], uint32_t len) {
+#pragma unroll
+    for (int j = 0; j < kDecodeChecks; ++j) T[j] = (uint32_t)j < len ? T[j] : 0;
+}
+
+// decode_roots among the non-erased positions: inv_gamma[i] == 0 marks an erased one
+SDA_HD uint32_t decode_roots_live(const uint64_t (&C)[kDecodeErrors + 1], uint32_t cap, uint32_t n_rows, const uint64_t* __restrict__ xs,
+                                  const uint64_t* __restrict__ inv_gamma, uint64_t p, uint64_t pinv, uint16_t* pos, uint32_t stride) {
+    uint32_t roots = 0;
+    for (uint32_t i = 0; i < n_rows; ++i) {
+        const uint64_t x = xs[i];
+        uint64_t acc = C[0];
+#pragma unroll
+        for (int j = 1; j <= kDecodeErrors; ++j)
+            if ((uint32_t)j <= cap) acc = addmod(dec_mm(acc, x, p, pinv), C[j], p);
+        if (acc == 0 && inv_gamma[i] != 0) {
+            if (roots < (uint32_t)kDecodeErrors) pos[roots * stride] = (uint16_t)i;
+            ++roots;
+        }
+    }
+    return roots;
+}
+
+// S_d -= Y X^d, d < f: a located error taken out of the sums the erased magnitudes are solved from
+SDA_HD void erase_remove(uint64_t (&S)[kDecodeChecks], uint32_t f, uint64_t Y, uint64_t X, uint64_t p, uint64_t pinv) {
+    uint64_t pw = Y;
+#pragma unroll
+    for (int d = 0; d < kDecodeChecks; ++d) {
+        if ((uint32_t)d < f) {
+            S[d] = submod(S[d], pw, p);
+            pw = dec_mm(pw, X, p, pinv);
+        }
+    }
+}
+
+// Ye[j] = sum_{m < f} rows[16 j + m] S_m, j < f (0 from f on): the erased magnitudes.  The rows are walked by a rolled loop and
+// Ye rotates one place per row - sixteen rotations leave row j's result at Ye[j] - so that no array is indexed at run time.
+SDA_HD void erase_magnitudes(const uint64_t (&S)[kDecodeChecks], uint32_t f, const uint64_t* __restrict__ rows, uint64_t p, uint64_t pinv,
+                             uint64_t (&Ye)[kEraseMax]) {
+#pragma unroll
+    for (int j = 0; j < kEraseMax; ++j) Ye[j] = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)kEraseMax; ++j) {
+        uint64_t y = 0;
+        if (j < f) {
+            const uint64_t* row = rows + (size_t)kEraseMax * j;
+            U128 acc = mul64x64(row[0], S[0]);
+#pragma unroll
+            for (int m = 1; m < kEraseMax; ++m) {
+                if ((uint32_t)m < f) {
+                    mac128(acc, row[m], S[m]);
+                    mont_acc_condsub(acc, p);              // 16 p^2 can pass p 2^64
+                }
+            }
+            y = mont_redc(acc, p, pinv);
+        }
+#pragma unroll
+        for (int i = 0; i + 1 < kEraseMax; ++i) Ye[i] = Ye[i + 1];
+        Ye[kEraseMax - 1] = y;
+    }
+}
+
+// v - sum_{j < f} corr[epos_j] Ye[j]: the erased positions' share of one secret's correction (corr = that secret's row of the table)
+SDA_HD uint64_t erase_apply(uint64_t v, const uint64_t* __restrict__ corr, const uint64_t* __restrict__ table, uint32_t f,
+                            const uint64_t (&Ye)[kEraseMax], uint64_t p, uint64_t pinv) {
+#pragma unroll
+    for (int j = 0; j < kEraseMax; ++j)
+        if ((uint32_t)j < f) v = submod(v, dec_mm(corr[table[kErasePos + j]], Ye[j], p, pinv), p);
+    return v;
 }
 
 }  // namespace sda

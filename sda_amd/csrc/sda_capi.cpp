@@ -1741,6 +1741,7 @@ struct sda_secret_reconstructor {
     // the sums [batches][k + job_checks] - and finish_checked_dev reads the two tables.  0: a plain job
     uint32_t job_checks = 0;
     DevBuf d_corr, d_xs, d_report;       // [k][n_rows] R[s][i] / u_i and [n_rows] x_i, Montgomery form; reconstruct_checked's report
+    DevBuf d_erase, d_flags;             // the erasure finish's per-job tables; reconstruct_erasures' flags as device words
     std::vector<uint64_t> h_R;           // d_R's content (have_R), for the tables of a checked job
     WeightedJob job() const {
         return WeightedJob{d_Rt.as<uint64_t>(), k + job_checks, (uint64_t)((dimension + k - 1) / k), mod.m, mod.mu, mont.pinv};
@@ -2114,16 +2115,20 @@ extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstruct
     return SDA_OK;
 }
 
-// The end of a checked job, one body for both finishes: the locating one (report [4 + rows], one head word at 2^64 - 1) or, with
-// `decode`, the decoding one with max_errors, 0 = checks / 2 (report [16 + rows], two such words).  A refused call leaves the
-// job as it was.
-static int finish_with_checks(sda_secret_reconstructor* r, bool decode, unsigned max_errors, int policy, int64_t* d_out, size_t out_cap,
-                              uint64_t* d_report, void* stream) {
+// The end of a checked job, one body for the three finishes: the locating one (report [4 + rows], one head word at 2^64 - 1), the
+// decoding one with max_errors, 0 = checks / 2 (report [16 + rows], two such words), or the erasure one, which decodes around the
+// positions d_ok marks (0 = erased, device words read by the kernels alone; NULL: none) and takes a job of one check too.  A refused
+// call leaves the job as it was.
+enum class CheckedEnd { Locate, Decode, Erasures };
+static int finish_with_checks(sda_secret_reconstructor* r, CheckedEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
+                              int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
+    const bool decode = end != CheckedEnd::Locate;
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
     if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
     if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
-    if (decode && r->job_checks < 2) return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
+    if (end == CheckedEnd::Decode && r->job_checks < 2)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
     if (decode && max_errors > r->job_checks / 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
     if (!policy_known(policy)) return fail_policy(policy);
@@ -2136,7 +2141,13 @@ static int finish_with_checks(sda_secret_reconstructor* r, bool decode, unsigned
     HIP_TRY(hipMemsetAsync(d_report, 0, words * 8, s));
     HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, decode ? 16 : 8, s));         // no bad batch and, decoding, no undecoded batch yet
     const size_t batches = (r->dimension + r->k - 1) / r->k;
-    if (decode)
+    if (end == CheckedEnd::Erasures) {
+        SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
+        HIP_TRY(launch_reveal_erasure_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                             r->d_xs.as<uint64_t>(), d_ok, r->d_erase.as<uint64_t>(), r->k, r->job_checks,
+                                             (uint32_t)r->job_rows, max_errors, policy == SDA_CHECK_CORRECT, batches, r->dimension, r->mod,
+                                             r->mont, d_out, d_report, s));
+    } else if (decode)
         HIP_TRY(launch_reveal_decode_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
                                             r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows,
                                             max_errors ? max_errors : r->job_checks / 2, policy == SDA_CHECK_CORRECT, batches, r->dimension,
@@ -2145,16 +2156,20 @@ static int finish_with_checks(sda_secret_reconstructor* r, bool decode, unsigned
         HIP_TRY(launch_reveal_check_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
                                            r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows, policy == SDA_CHECK_CORRECT,
                                            batches, r->dimension, r->mod, r->mont, d_out, d_report, s));
-    NOTE_CALL_KERNELS("%s", decode ? "reveal_decode_finish_kernel" : "reveal_check_finish_kernel");
+    NOTE_CALL_KERNELS("%s", end == CheckedEnd::Erasures ? "reveal_erasure_setup_kernel + reveal_erasure_finish_kernel"
+                            : decode                  ? "reveal_decode_finish_kernel"
+                                                      : "reveal_check_finish_kernel");
     r->job_begun = false;
     r->job_checks = 0;
     return SDA_OK;
 }
 
-// reconstruct_checked / reconstruct_decoded: host rows through one checked job, the secrets and the report back to the host
+// reconstruct_checked / reconstruct_decoded / reconstruct_erasures: host rows through one checked job, the secrets and the report
+// back to the host.  erased (the erasure form only; NULL: none): n_rows host bytes, non-zero = erased
 static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* indices, const int64_t* const* rows, const size_t* row_lens,
-                                   size_t n_rows, unsigned checks, bool decode, unsigned max_errors, int policy, int64_t* out,
-                                   size_t out_cap, size_t* out_len, uint64_t* report) {
+                                   size_t n_rows, unsigned checks, CheckedEnd end, const uint8_t* erased, unsigned max_errors, int policy,
+                                   int64_t* out, size_t out_cap, size_t* out_len, uint64_t* report) {
+    const bool decode = end != CheckedEnd::Locate;
     if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     *out_len = 0;
     if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
@@ -2162,7 +2177,9 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
     if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
     if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
     if (!policy_known(policy)) return fail_policy(policy);
-    if (decode && (checks < 2 || max_errors > checks / 2))
+    if (end == CheckedEnd::Erasures && max_errors > checks / 2)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: at most checks / 2 positions are decoded", checks, max_errors);
+    if (end == CheckedEnd::Decode && (checks < 2 || max_errors > checks / 2))
         return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: decoding takes at least 2 checks and at most checks / 2 positions", checks, max_errors);
     const size_t batches = (r->dimension + r->k - 1) / r->k;
     for (size_t i = 0; i < n_rows; ++i)
@@ -2175,7 +2192,16 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
     SDA_TRY(stage_packed_rows(r, rows, n_rows, batches, &stride));
     SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
     SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
-    SDA_TRY(finish_with_checks(r, decode, max_errors, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
+    const uint32_t* d_ok = nullptr;
+    if (end == CheckedEnd::Erasures && erased) {
+        std::vector<uint32_t> ok(n_rows);
+        for (size_t i = 0; i < n_rows; ++i) ok[i] = erased[i] ? 0u : 1u;
+        SDA_TRY(r->d_flags.reserve(n_rows * 4));
+        HIP_TRY(hipMemcpyAsync(r->d_flags.p, ok.data(), n_rows * 4, hipMemcpyHostToDevice, r->ctx.stream));
+        HIP_TRY(hipStreamSynchronize(r->ctx.stream));                        // `ok` is a local vector
+        d_ok = r->d_flags.as<uint32_t>();
+    }
+    SDA_TRY(finish_with_checks(r, end, d_ok, max_errors, policy, r->d_out.as<int64_t>(), r->dimension, r->d_report.as<uint64_t>(), nullptr));
     if (r->dimension) HIP_TRY(hipMemcpyAsync(out, r->d_out.p, r->dimension * 8, hipMemcpyDeviceToHost, r->ctx.stream));
     HIP_TRY(hipMemcpyAsync(report, r->d_report.p, words * 8, hipMemcpyDeviceToHost, r->ctx.stream));
     SDA_TRY(r->ctx.sync());
@@ -2185,14 +2211,14 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
 
 extern "C" int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
                                                            uint64_t* d_report, void* stream) {
-    return finish_with_checks(r, false, 0, policy, d_out, out_cap, d_report, stream);
+    return finish_with_checks(r, CheckedEnd::Locate, nullptr, 0, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
                                                             uint64_t* report) {
-    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, false, 0, policy, out, out_cap, out_len, report);
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Locate, nullptr, 0, policy, out, out_cap, out_len, report);
 }
 
 // ---- the decoding finish: up to floor(checks / 2) faulty positions per batch, from the same syndromes ---------------------------
@@ -2200,14 +2226,33 @@ extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstru
 // whose solution with |E| <= checks / 2 is unique.  The kernel solves it per batch (reveal_decode.hpp); the tables are begin_checked_dev's.
 extern "C" int sda_secret_reconstructor_finish_decoded_dev(sda_secret_reconstructor_t* r, unsigned max_errors, int policy, int64_t* d_out,
                                                            size_t out_cap, uint64_t* d_report, void* stream) {
-    return finish_with_checks(r, true, max_errors, policy, d_out, out_cap, d_report, stream);
+    return finish_with_checks(r, CheckedEnd::Decode, nullptr, max_errors, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, unsigned max_errors, int policy, int64_t* out,
                                                             size_t out_cap, size_t* out_len, uint64_t* report) {
-    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, true, max_errors, policy, out, out_cap, out_len, report);
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Decode, nullptr, max_errors, policy, out, out_cap, out_len,
+                                   report);
+}
+
+// ---- the erasure finish: positions the caller knows to be unreliable cost one check each, not two ---------------------------------
+// A row that update_sealed_rows_dev refused (d_ok[r] = 0) added nothing; its position is known, so it is an erasure.  With the f
+// erased positions F and Gamma(z) = prod_{j in F} (z - x_j) the modified syndromes T_j = sum_m gamma_m S_{j+m}, j < checks - f,
+// no longer see F, decode up to floor((checks - f) / 2) further faulty positions, and the erased magnitudes follow from
+// S_0 .. S_{f-1}.  d_ok stays on the device: reveal_erasure_setup_kernel reads it, and the host never learns f.
+extern "C" int sda_secret_reconstructor_finish_erasures_dev(sda_secret_reconstructor_t* r, const uint32_t* d_ok, unsigned max_errors,
+                                                            int policy, int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
+    return finish_with_checks(r, CheckedEnd::Erasures, d_ok, max_errors, policy, d_out, out_cap, d_report, stream);
+}
+
+extern "C" int sda_secret_reconstructor_reconstruct_erasures(sda_secret_reconstructor_t* r, const size_t* indices,
+                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
+                                                             unsigned checks, const uint8_t* erased, unsigned max_errors, int policy,
+                                                             int64_t* out, size_t out_cap, size_t* out_len, uint64_t* report) {
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Erasures, erased, max_errors, policy, out, out_cap,
+                                   out_len, report);
 }
 
 // =================================================================================================

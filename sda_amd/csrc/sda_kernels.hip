@@ -1518,6 +1518,212 @@ __global__ __launch_bounds__(kThreads) void reveal_decode_finish_kernel(RevealDe
     }
 }
 
+// The ERASURE finish of a checked job (sda_secret_reconstructor_finish_erasures_dev), part 1: what depends on the job and the
+// erased set F alone.  One workgroup.  It compacts the zero words of `ok` in ascending order - 256 positions per step, ballots per
+// wave, the waves' counts through LDS - counts f in full and keeps the first 16 positions; f > checks sets the overflow word and
+// nothing else is built.  Otherwise lane 0 multiplies Gamma out (at most 152 products), and the Fermat powers - one per erased
+// point for its row g_{j,m} / Gamma_j(x_j), one per position for 1 / Gamma(x_i) - are spread over the lanes, the rows from the
+// last lane downwards, the positions from the first upwards.  The table (reveal_decode.hpp) is in Montgomery form; f and the
+// overflow word also go to the report's words [6] and [7], which the caller has zeroed on this stream.
+__global__ __launch_bounds__(kThreads) void reveal_erasure_setup_kernel(const uint32_t* __restrict__ ok, const uint64_t* __restrict__ xs,
+                                                                        uint32_t n_rows, uint32_t checks, uint64_t p, uint64_t pinv,
+                                                                        uint64_t one, uint64_t* __restrict__ table,
+                                                                        unsigned long long* __restrict__ report) {
+    __shared__ uint32_t wave_n[kThreads / 64];
+    __shared__ uint32_t count;
+    __shared__ uint32_t epos[kEraseMax];
+    __shared__ uint64_t gam[kEraseMax + 1];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) count = 0;
+    if (tid < (uint32_t)kEraseMax) epos[tid] = 0;
+    __syncthreads();
+    if (ok != nullptr) {
+        for (uint32_t base = 0; base < n_rows; base += kThreads) {             // uniform: every lane reaches the barriers
+            const uint32_t i = base + tid;
+            const bool erased = i < n_rows && ok[i] == 0;
+            const unsigned long long mine = __ballot(erased);
+            if (lane == 0) wave_n[wave] = (uint32_t)__popcll(mine);
+            __syncthreads();
+            uint32_t at = count;
+            for (uint32_t w = 0; w < wave; ++w) at += wave_n[w];
+            at += (uint32_t)__popcll(mine & ((1ull << lane) - 1));
+            if (erased && at < (uint32_t)kEraseMax) epos[at] = i;
+            __syncthreads();
+            if (tid == 0) count += wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];   // at most n_rows <= 65535
+            __syncthreads();
+        }
+    }
+    static_assert(kThreads / 64 == 4, "the sum of the waves' counts above");
+    const uint32_t f = count;
+    const bool over = f > checks;
+    if (tid == 0) {
+        table[kEraseCount] = f;
+        table[kEraseOver] = over ? 1 : 0;
+        report[6] = f;
+        report[7] = over ? 1 : 0;
+    }
+    if (tid < (uint32_t)kEraseMax) table[kErasePos + tid] = epos[tid];
+    if (over) return;                                                          // uniform
+    if (tid == 0) erase_gamma(xs, epos, f, one, p, pinv, gam);
+    __syncthreads();
+    const uint32_t back = (uint32_t)kThreads - 1 - tid;
+    if (back < f) erase_solve_row(gam, f, xs[epos[back]], p, pinv, table + kEraseRows + (size_t)kEraseMax * back);
+    for (uint32_t i = tid; i < n_rows; i += kThreads) table[kEraseInv + i] = erase_inv_gamma(gam, f, xs[i], p, pinv);
+}
+
+// Part 2, one lane per batch with the structure of reveal_decode_finish_kernel.  f and the overflow word are read from the table
+// (wave-uniform, as every table entry but 1 / Gamma at a located position).  The lane folds S, folds the f erased points into a
+// copy T and keeps T_0 .. T_{c-f-1}: all zero = the batch is consistent, else bad, and T is decoded with at most
+// min(cap, floor((c - f) / 2)) non-erased positions, Y = Z / Gamma(x).  Under SDA_CHECK_CORRECT a consistent or decoded batch
+// with a non-zero S takes its errors out of S_0 .. S_{f-1}, solves the erased magnitudes by f dot products - they stay in sixteen
+// registers walked by unrolled loops, the erased positions are the table's - and its secrets lose the correction over E u F.
+// Located positions and magnitudes live in LDS columns as in the sibling: no scratch.  On overflow the lane folds and stores.
+struct RevealErasureJob {
+    const uint64_t* lo;          // [batches][k + checks]
+    const int64_t* hi;
+    const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
+    const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
+    const uint64_t* table;       // reveal_erasure_setup_kernel's
+    uint32_t k, checks, n_rows, correct, cap;
+    uint64_t batches, dimension;
+    ModParams mod;
+    uint64_t pinv;
+};
+
+__global__ __launch_bounds__(kThreads) void reveal_erasure_finish_kernel(RevealErasureJob J, int64_t* __restrict__ out,
+                                                                         unsigned long long* __restrict__ report) {
+    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
+    __shared__ unsigned int wg_most;                       // the largest nu
+    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
+    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
+    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
+    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        wg_most = 0;
+        wg_first[0] = wg_first[1] = ~0ull;
+    }
+    __syncthreads();
+    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = b < J.batches;
+    const int lane = threadIdx.x & 63;
+    const uint32_t width = J.k + J.checks;
+    const uint64_t* lo = J.lo + (live ? b : 0) * width;
+    const int64_t* hi = J.hi + (live ? b : 0) * width;
+    const uint64_t m = J.mod.m;
+    const bool over = J.table[kEraseOver] != 0;
+    const uint32_t f = over ? 0 : (uint32_t)J.table[kEraseCount];             // <= checks from here on
+    const uint32_t len = J.checks - f;                                         // the modified syndromes
+    const uint32_t cap = J.cap < len / 2 ? J.cap : len / 2;
+
+    uint64_t S[kMaxChecks], T[kMaxChecks];
+#pragma unroll
+    for (int g = 0; g < kMaxChecks / 4; ++g) {
+        uint64_t o[4] = {0, 0, 0, 0};
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[4 * g + j] = T[4 * g + j] = o[j];        // 0 from J.checks on
+    }
+#pragma unroll 1
+    for (uint32_t q = 0; q < f; ++q) erase_fold_point(T, J.checks, J.xs[J.table[kErasePos + q]], m, J.pinv);
+    erase_keep(T, len);
+    uint64_t any = 0, any_s = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxChecks; ++d) {
+        any |= T[d];
+        any_s |= S[d];
+    }
+    const bool bad = live && !over && any != 0;
+
+    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
+    if (bad && cap >= 1) {
+        uint64_t C[kDecodeErrors + 1];
+        const uint32_t L = decode_bm(T, len, m, J.pinv, C);
+        if (L >= 1 && L <= cap &&
+            decode_roots_live(C, cap, J.n_rows, J.xs, J.table + kEraseInv, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L) {
+            uint64_t Om[kDecodeErrors];
+            decode_omega(T, C, cap, m, J.pinv, Om);
+            for (uint32_t j = 0; j < L; ++j) {
+                const uint32_t at = dec_pos[j][threadIdx.x];
+                const uint64_t Z = decode_magnitude(C, Om, L, J.xs[at], m, J.pinv);
+                dec_y[j][threadIdx.x] = dec_mm(Z, J.table[kEraseInv + at], m, J.pinv);
+            }
+            nu = L;
+        }
+    }
+    const bool decoded = nu != 0;
+    const bool fix = decoded && J.correct != 0;
+    // the erased positions' share: a consistent or decoded batch whose sums are not all zero
+    const bool mend = live && f != 0 && J.correct != 0 && any_s != 0 && (!bad || decoded);
+    uint64_t Ye[kEraseMax];
+#pragma unroll
+    for (int j = 0; j < kEraseMax; ++j) Ye[j] = 0;
+    if (mend) {
+        for (uint32_t q = 0; q < nu; ++q) erase_remove(S, f, dec_y[q][threadIdx.x], J.xs[dec_pos[q][threadIdx.x]], m, J.pinv);
+        erase_magnitudes(S, f, J.table + kEraseRows, m, J.pinv, Ye);
+    }
+
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t e = b * J.k + s0 + j;
+            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
+            uint64_t v = o[j];
+            const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
+            if (fix) {
+                for (uint32_t q = 0; q < nu; ++q)
+                    v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
+            }
+            if (mend) v = erase_apply(v, corr, J.table, f, Ye, m, J.pinv);
+            out[e] = (int64_t)v;
+        }
+    }
+
+    // ---- the report: the sibling's ----
+    const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
+    const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
+    if (lane == 0 && bad_lanes != 0) {
+        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
+        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
+        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
+        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
+    }
+    if (decoded_lanes != 0) {                              // wave-uniform
+        for (uint32_t j = 0; j < cap; ++j) {
+            const unsigned long long with = __ballot(nu == j + 1);
+            if (lane == 0 && with != 0) {
+                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
+                atomicMax(&wg_most, j + 1);
+            }
+            const bool has = j < nu;
+            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
+            unsigned long long pending = __ballot(has);
+            while (pending) {                              // one atomic per distinct position the wave blames in slot j
+                const int leader = __ffsll((long long)pending) - 1;
+                const uint32_t pos = (uint32_t)__shfl((int)mine, leader);
+                const unsigned long long same = __ballot(has && mine == pos);
+                if (lane == leader) atomicAdd(&report[16 + pos], (unsigned long long)__popcll(same));
+                pending &= ~same;
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
+        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
+        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
+        atomicMin(&report[3], wg_first[0]);
+        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
+        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
+        for (int j = 0; j < kDecodeErrors; ++j)
+            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
+    }
+}
+
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
 // =================================================================================================
@@ -2546,6 +2752,27 @@ hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* 
     if (hipError_t e = grid_check(blocks)) return e;
     const RevealDecodeJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, max_errors, batches, dimension, mod, mont.pinv};
     reveal_decode_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
+    return hipGetLastError();
+}
+
+size_t reveal_erasure_table_words(size_t n_rows) { return erase_table_words(n_rows); }
+
+hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
+                                        const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks, uint32_t n_rows,
+                                        uint32_t max_errors, bool correct, size_t batches, size_t dimension, const ModParams& mod,
+                                        const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
+    if (checks == 0 || checks > (uint32_t)kMaxChecks || max_errors > checks / 2 || n_rows == 0 || n_rows > 65535)   // dec_pos is 16 bits wide
+        return hipErrorInvalidValue;
+    const uint64_t blocks = ceil_div(batches, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    const uint64_t one = h_to_mont(1, mont.p);
+    reveal_erasure_setup_kernel<<<dim3(1), dim3(kThreads), 0, s>>>(d_ok, d_xs, n_rows, checks, mont.p, mont.pinv, one, d_table,
+                                                                   reinterpret_cast<unsigned long long*>(d_report));
+    if (hipError_t e = hipGetLastError()) return e;
+    if (batches == 0) return hipSuccess;
+    const RevealErasureJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, d_table, k, checks, n_rows, correct ? 1u : 0u,
+                             max_errors ? max_errors : (uint32_t)kDecodeErrors, batches, dimension, mod, mont.pinv};
+    reveal_erasure_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
     return hipGetLastError();
 }
 

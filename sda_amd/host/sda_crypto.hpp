@@ -441,6 +441,32 @@ struct SecretReconstructor {
         c.out.resize(c.n_out);
         return {std::move(c.out), RevealDecode::from_words(c.words)};
     }
+    // the erasure finish of a checked job: positions known to be unreliable - the rows a sealed update refused - cost one check each,
+    // not two.  d_ok: n_rows device words, 0 = erased (what update_sealed_rows_dev writes; nullptr: none), read by the kernels alone.
+    // d_report as for finish_decoded_dev, [6] = the number of erased positions, [7] = 1 when they are more than checks
+    void finish_erasures_dev(const uint32_t* d_ok, int64_t* d_out, size_t out_cap, uint64_t* d_report, unsigned max_errors = 0,
+                             bool correct = false, void* stream = nullptr) {
+        detail::check(sda_secret_reconstructor_finish_erasures_dev(h, d_ok, max_errors, correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, d_out,
+                                                                   out_cap, d_report, stream));
+    }
+    struct Erasures {
+        std::vector<Secret> values;
+        RevealDecode decode;
+        uint64_t erased = 0;                                                  // as the device counted them
+        bool unrepaired = false;                                              // more erased rows than checks
+    };
+    // erased: one byte per row, non-zero = erased; empty = none
+    Erasures reconstruct_erasures(const std::vector<std::pair<size_t, std::vector<Share>>>& indexed_shares, const std::vector<uint8_t>& erased,
+                                  unsigned checks, unsigned max_errors = 0, bool correct = false) const {
+        if (!erased.empty() && erased.size() != indexed_shares.size()) detail::check(SDA_ERR_INVALID_ARGUMENT);
+        HostCall c(indexed_shares, dimension, sda_reconstruct_decode_report_words(indexed_shares.size()));
+        detail::check(sda_secret_reconstructor_reconstruct_erasures(h, c.idx.data(), c.ptrs.data(), c.lens.data(), c.idx.size(), checks,
+                                                                    erased.empty() ? nullptr : erased.data(), max_errors,
+                                                                    correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, c.out.data(), dimension,
+                                                                    &c.n_out, c.words.data()));
+        c.out.resize(c.n_out);
+        return {std::move(c.out), RevealDecode::from_words(c.words), c.words[6], c.words[7] != 0};
+    }
 
 private:
     // the arguments of a host reconstruct call: indexed_shares unpacked, the output and the report sized
