@@ -78,6 +78,11 @@ int  sda_debug_stream_create(void** stream);
 int  sda_debug_stream_destroy(void* stream);
 int  sda_debug_stream_synchronize(void* stream);
 int  sda_debug_mem_info(size_t* free_bytes, size_t* total_bytes);
+/* What the library's handles hold on the device right now, process-wide: the number of live device buffers the handles allocated
+ * for themselves (every handle type of include/sda_hip.h, the sealed box's scratch included) and their bytes as allocated.  Memory
+ * the caller owns (sda_dev_malloc) is not counted.  A handle that is freed must give back everything it took: the figures are the
+ * library's own books, so they do not move when another process allocates.  For tests/test_handle_release_gpu.py. */
+int  sda_debug_live_device_buffers(size_t* buffers, size_t* bytes);
 /* Poly1305 with a CHOSEN one-time key, through the sealed-box kernels (sbox_poly_kernel and sbox_final_kernel, unchanged): the
  * tags of `rows` device messages (row r at d_msgs + r * msg_slot, d_msg_bytes[r] <= max_msg_bytes bytes; buffer and slot
  * 16-byte aligned) under the `rows` 32-byte keys (r || s) of the HOST array `keys`, written to the HOST array `tags` (16 bytes

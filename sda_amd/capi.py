@@ -263,6 +263,7 @@ HOOK_SIGNATURES = {
     "sda_debug_stream_destroy": (C.c_int, [C.c_void_p]),
     "sda_debug_stream_synchronize": (C.c_int, [C.c_void_p]),
     "sda_debug_mem_info": (C.c_int, [c_sizep, c_sizep]),
+    "sda_debug_live_device_buffers": (C.c_int, [c_sizep, c_sizep]),
     "sda_debug_select_path": (C.c_int, [_SS, C.c_char_p, C.c_char_p, C.c_size_t]),
     "sda_debug_last_reveal_kernel": (C.c_char_p, []),
     "sda_debug_poly1305_rows_dev": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_char_p]),

@@ -284,6 +284,26 @@ extern "C" int sda_device_pci_bus_id(int ordinal, char* out, size_t cap) {
     return SDA_OK;
 }
 
+// What the handles hold on the device: every buffer a handle allocates for itself (DevBuf below, the sealed box's scratch in
+// sda_sealedbox.cpp) is noted when it is allocated and when it is freed.  The test library keeps the process-wide count
+// (sda_debug_live_device_buffers, include/sda_hip_debug.h); the release library counts nothing.  Caller-owned sda_dev_malloc
+// memory is not a handle's and is not noted.
+namespace sda { void note_device_buffer(bool allocated, size_t bytes); }
+#ifdef SDA_TEST_HOOKS
+static std::atomic<size_t> g_live_buffers{0}, g_live_bytes{0};
+void sda::note_device_buffer(bool allocated, size_t bytes) {
+    if (allocated) { g_live_buffers.fetch_add(1); g_live_bytes.fetch_add(bytes); }
+    else { g_live_buffers.fetch_sub(1); g_live_bytes.fetch_sub(bytes); }
+}
+extern "C" int sda_debug_live_device_buffers(size_t* buffers, size_t* bytes) {
+    if (!buffers || !bytes) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
+    *buffers = g_live_buffers.load(); *bytes = g_live_bytes.load();
+    return SDA_OK;
+}
+#else
+void sda::note_device_buffer(bool, size_t) {}
+#endif
+
 namespace {
 
 struct Ctx {
@@ -323,11 +343,12 @@ struct DevBuf {
     size_t cap = 0;
     int reserve(size_t bytes) {
         if (bytes <= cap) return SDA_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        if (p) { (void)hipFree(p); note_device_buffer(false, cap); p = nullptr; cap = 0; }
         size_t want = bytes < 256 ? 256 : bytes;
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) { p = nullptr; return fail(SDA_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
         cap = want;
+        note_device_buffer(true, cap);
         return SDA_OK;
     }
     // ... for a buffer that holds key material while it grows: the old allocation is zeroed before it is freed
@@ -336,7 +357,7 @@ struct DevBuf {
         return reserve(bytes);
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) { (void)hipFree(p); note_device_buffer(false, cap); }
         p = nullptr; cap = 0;
     }
     // for buffers that held secrets, shares, randomness or seeds: zero the memory before it returns to the allocator
@@ -1786,6 +1807,7 @@ extern "C" void sda_secret_reconstructor_free(sda_secret_reconstructor_t* r) {
     if (r->ctx.device >= 0) (void)hipSetDevice(r->ctx.device);
     r->acc.release(); r->tile.release(); r->d_out.release(); r->d_R.release(); r->d_R31.release(); r->d_shares.release();
     r->job_acc.release(); r->d_Rt.release(); r->d_corr.release(); r->d_xs.release(); r->d_report.release();
+    r->d_erase.release(); r->d_flags.release();
     r->ctx.destroy();
     delete r;
 }

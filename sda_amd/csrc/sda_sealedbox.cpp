@@ -25,16 +25,20 @@ struct sda_sealedbox {
     void* d_lens = nullptr; size_t lens_cap = 0;           // message lengths: of a verify-only pass (nobody reads them), of a fused seal
 };
 
+namespace sda { void note_device_buffer(bool allocated, size_t bytes); }      // sda_capi.cpp: counted by the test library only
+
 namespace {
 int reserve(void*& p, size_t& cap, size_t bytes, bool wipe) {
     if (bytes <= cap) return SDA_OK;
     if (p) {
         if (wipe) (void)hipMemset(p, 0, cap);
         (void)hipFree(p);
+        note_device_buffer(false, cap);
         p = nullptr; cap = 0;
     }
     if (hipMalloc(&p, bytes < 256 ? 256 : bytes) != hipSuccess) { p = nullptr; return capi_fail(SDA_ERR_ALLOC, "hipMalloc(%zu) failed", bytes); }
     cap = bytes < 256 ? 256 : bytes;
+    note_device_buffer(true, cap);
     return SDA_OK;
 }
 int scratch(sda_sealedbox* b, size_t rows, size_t max_msg) {
@@ -94,7 +98,7 @@ extern "C" void sda_sealedbox_free(sda_sealedbox_t* b) {
     void* bufs[5] = {b->d_states, b->d_partial, b->d_keys, b->d_io, b->d_lens};
     size_t caps[5] = {b->states_cap, b->partial_cap, b->keys_cap, b->io_cap, b->lens_cap};
     for (int i = 0; i < 5; ++i)
-        if (bufs[i]) { (void)hipMemset(bufs[i], 0, caps[i]); (void)hipFree(bufs[i]); }      // key-derived material: wiped
+        if (bufs[i]) { (void)hipMemset(bufs[i], 0, caps[i]); (void)hipFree(bufs[i]); note_device_buffer(false, caps[i]); }      // key-derived material: wiped
     delete b;
 }
 

@@ -21,6 +21,9 @@ SCHEMES = {
     "k3_31": (P31, 3, 4, 8, 495332030, 1761729792),                 # tss-valid (3, 4, 8), tests/test_path_select.py:62
     "k8_62": (P62, 8, 2, 26, W62[16], W62[27]),
     "pss155": (TSS_P, 100, 155, 728, TSS_W2, TSS_W3),
+    # a wide committee over the 62-bit prime: extremes.omegas(P62, 3, 1, 300) - any distinct nodes, all the library asks for
+    # (tests/test_reveal_erasure_reach.py recomputes the two literals)
+    "k3_wide": (P62, 3, 1, 300, 2177342806168468507, 4354685612336937012),
     "additive": (P62, 1, 0, 3, 0, 0),
 }
 

@@ -30,20 +30,26 @@ MAX_CHECKS = 16                              # SDA_RECONSTRUCT_MAX_CHECKS
 #         p (one row moved by exactly p)
 # feed  : how the SEALED run is fed ("one" call / "descending", one position per call); every case also runs all-plaintext and mixed
 # expect: the verdict the case is there for - clean | located | unlocated | None (whatever the model says)
-Case = collections.namedtuple("Case", "name scheme dim indices checks values fault feed surplus expect")
+# pin   : the faulty positions, where the case fixes them (None: drawn from the case's seeded generator, as ever)
+#
+# fault "steered" (reveal_decode_cases.steer): batch b gets errors on `checks` pinned positions whose syndromes are a geometric
+# sequence a r^d - r = the first pinned point (one error there: located), a value that is no point (unlocated), the node 1 that is
+# no row (unlocated) for b mod 3 = 0, 1, 2
+Case = collections.namedtuple("Case", "name scheme dim indices checks values fault feed surplus expect pin", defaults=(None,))
 
 ALL8 = tuple(range(8))
 FIVE = (7, 0, 3, 5, 1)                                                  # k3_62: r = 1
 K8_ALL = tuple(range(26))                                              # k8_62: r = 16
 K8_TWELVE = (25, 0, 13, 7, 1, 19, 4, 22, 10, 16, 2, 11)                # k8_62: r = 2
+WIDE_300, WIDE_257 = tuple(range(300)), tuple(range(257))              # k3_wide: r = 296 and 253, positions past a byte
 PSS_260 = tuple((37 * i + 5) % 728 for i in range(260))                # pss155: r = 5, scattered (gcd(37, 728) = 1)
 
 
 def _cases():
     out = []
 
-    def add(name, scheme, dim, indices, checks, values="sums", fault="none", feed="one", surplus=0, expect=None):
-        out.append(Case(name, scheme, dim, indices, checks, values, fault, feed, surplus, expect))
+    def add(name, scheme, dim, indices, checks, values="sums", fault="none", feed="one", surplus=0, expect=None, pin=None):
+        out.append(Case(name, scheme, dim, indices, checks, values, fault, feed, surplus, expect, pin))
     # config 3's committee, all 8 rows: 1, 2 and 4 checks at every dimension at which the finish takes another path - one batch, no
     # padding, padding, 334 batches (two workgroups; at k + checks = 7 past the 2048-column window of the sealed kernel), 2101
     for dim in (1, 3, 4, 1000, 6301):
@@ -87,6 +93,18 @@ def _cases():
     add("pss155-c5-d250-two", "pss155", 250, PSS_260, 5, fault="two", expect="unlocated")
     add("pss155-c5-d250-first", "pss155", 250, PSS_260, 5, fault="first", feed="descending", expect="located")
     add("pss155-c2-d250-two", "pss155", 250, PSS_260, 2, fault="two", expect="unlocated")
+    # a wide committee over the 62-bit prime (300 rows, k = 3, t = 1): k + checks = 5, 16 (LDS coefficients) and 19 (global); 257
+    # batches (two workgroups, a store tail).  The faulty positions are pinned at and past 256 - the blame word report[4 + pos], the
+    # column of corr - and at the last row
+    for checks, row, two in ((2, (299,), (255, 256)), (13, (256,), (64, 299)), (16, (257,), (256, 299))):
+        add(f"k3_wide-c{checks}-d769-clean", "k3_wide", 769, WIDE_300, checks, expect="clean")
+        add(f"k3_wide-c{checks}-d769-row", "k3_wide", 769, WIDE_300, checks, fault="row", expect="located", pin=row,
+            feed="descending" if checks == 13 else "one")
+        add(f"k3_wide-c{checks}-d769-two", "k3_wide", 769, WIDE_300, checks, fault="two", expect="unlocated", pin=two)
+    add("k3_wide-257-c2-d769-row", "k3_wide", 769, WIDE_257, 2, fault="row", expect="located", pin=(256,))
+    add("k3_wide-c16-d1-row", "k3_wide", 1, WIDE_300, 16, fault="row", expect="located", pin=(299,))
+    # steered syndromes: the locate rule on geometric sequences whose ratio is a point, no point, and the node 1
+    add("k3_62-c4-d769-steered", "k3_62", 769, ALL8, 4, fault="steered", pin=(7, 0, 3, 5))
     return out
 
 
@@ -144,7 +162,7 @@ Finish = collections.namedtuple("Finish", "out report verdicts")
 def model_finish(case, rows, policy, plant=None):
     """what finish_checked_dev must store and report for any-int64 rows.  plant: a fault planted in the MODEL (tests only):
     "weight" (one wrong syndrome weight), "no_node1" (node 1 left out of u_i), "locate" (the locate loop stops one syndrome early),
-    "sign" (the correction added)"""
+    "sign" (the correction added), "position_mod_256" (the located position loses its high byte in blame and correction)"""
     T = tables(case.scheme, case.indices, case.checks, plant if plant in ("weight", "no_node1") else None)
     p, k, n_rows, checks = T.p, T.k, len(case.indices), case.checks
     B = batches(case)
@@ -166,7 +184,7 @@ def model_finish(case, rows, policy, plant=None):
                 fits = [i for i in range(n_rows) if all(S[d + 1] == T.x[i] * S[d] % p for d in range(pairs))]
                 if len(fits) == 1:
                     verdict = "located"
-                    c = fits[0]
+                    c = fits[0] % 256 if plant == "position_mod_256" else fits[0]
                     located += 1
                     blame[c] += 1
                     if policy == CORRECT:
@@ -221,6 +239,9 @@ def build(name):
     rows = clean.copy()
     c1, c2 = int(rng.integers(0, pos)), 0
     c2 = (c1 + 1 + int(rng.integers(0, pos - 1))) % pos
+    if case.pin is not None and case.fault != "steered":
+        c1 = case.pin[0]
+        c2 = case.pin[1] if len(case.pin) > 1 else (c1 + 1) % pos
     faulty = ()
     special = np.array([I64_MIN, I64_MAX, -1, -p, p - 1, 0, p, 1, I64_MIN + 1, -p - 1], dtype=np.int64)
     if case.values == "crafted":
@@ -256,6 +277,15 @@ def build(name):
     elif case.fault == "p":
         rows[c1, :B] += p                                        # below 2^62 + 2^62: no overflow
         assert not np.array_equal(rows[c1], clean[c1])
+    elif case.fault == "steered":
+        import reveal_decode_cases as dc                         # (it imports this module: only at the call)
+        T = tables(case.scheme, case.indices, case.checks)
+        z = dc.no_point(T, rng)
+        for b in range(B):
+            a = int(rng.integers(1, p))
+            ratio = (T.x[case.pin[0]], z, 1)[b % 3]
+            dc.steer(rows, T, case.pin, b, [a * pow(ratio, d, p) % p for d in range(case.checks)])
+        faulty = None                                            # the model alone says what comes out
     else:
         assert case.fault == "none"
     return Built(rows, clean, want, row_len, B, faulty)

@@ -32,20 +32,27 @@ ALL8, K8_ALL = vc.ALL8, vc.K8_ALL
 # erased: the erased positions F
 # errors: how many NON-erased rows are faulty in every batch, or "mixed": batch b is clean (erased rows hold their true values) /
 #         erasure-only / erasure + e' errors / erasure + e' + 1 errors (undecoded) for b mod 4 = 0 .. 3 - side by side in one wave
-#         or "aimed": two faulty rows whose modified syndromes are those of ONE error on the first erased position - a root the
+#         or "aimed": c - f faulty rows whose modified syndromes are those of ONE error on an erased position - a root the
 #         search must not accept
+#         or "steered": batch b holds errors on c - f pinned non-erased positions whose MODIFIED syndromes are exactly those of
+#         family b mod F of reveal_decode_cases.families(c - f)
 # fill  : what the erased rows hold - zero (a refused row adds nothing) | random | clean (their true values) | spoiled (true + error)
 # ok    : how the flags reach the call - flags (n_rows words) | ones (all non-zero) | null
 # cap   : max_errors as passed (0 = unlimited)
-Case = collections.namedtuple("Case", "name scheme dim indices checks cap erased errors fill ok")
+# pin   : non-erased positions that come first in the order the faulty rows are taken from (None: the seeded permutation alone, as
+#         ever); steered: the c - f positions the errors are planted on
+Case = collections.namedtuple("Case", "name scheme dim indices checks cap erased errors fill ok pin", defaults=(None,))
+WIDE_300, WIDE_257 = vc.WIDE_300, vc.WIDE_257
+STEP = 256                                   # positions reveal_erasure_setup_kernel compacts per step (kThreads), four waves of 64
+KEPT = 16                                    # erased positions it keeps (kEraseMax); f is counted in full
 
 
 def _cases():
     out = []
 
-    def add(tag, scheme, dim, indices, checks, erased=(), errors=0, fill="zero", ok="flags", cap=0, note=""):
+    def add(tag, scheme, dim, indices, checks, erased=(), errors=0, fill="zero", ok="flags", cap=0, note="", pin=None):
         name = f"{tag}-c{checks}-d{dim}-f{len(erased)}-e{errors}-{fill}" + (f"-cap{cap}" if cap else "") + ("" if ok == "flags" else "-" + ok) + note
-        out.append(Case(name, scheme, dim, tuple(indices), checks, cap, tuple(sorted(erased)), errors, fill, ok))
+        out.append(Case(name, scheme, dim, tuple(indices), checks, cap, tuple(sorted(erased)), errors, fill, ok, pin))
     # config 3's committee (8 rows, k = 3, t = 1), c = 4: every (f, errors) pair, at one batch, 255 and 257 batches (one workgroup
     # - 1 / + 1) with the three store tails (dim mod 3 = 1, 2, 0); the padding batch is decoded and not stored
     pairs = [(1, 0), (1, 1), (2, 0), (2, 1), (3, 0), (4, 0), (0, 1), (0, 2), (1, 2), (3, 1), (5, 0)]
@@ -91,12 +98,45 @@ def _cases():
     add("k8_62", "k8_62", 2053, K8_ALL, 16, some(6), 5)                      # 257 batches
     add("k8_62", "k8_62", 805, K8_ALL, 16, (), 8, ok="null")
     add("k8_62", "k8_62", 805, K8_ALL, 16, (), 3, ok="ones")
-    return out
+    parent = len(out)                                                  # the table up to here is older than the wide committee
+    # a wide committee over the 62-bit prime (300 rows, k = 3, t = 1; 257 batches): the setup kernel's second step (positions from
+    # 256), every wave of a step (64 positions each), the count carried from step to step, positions it counts and does not keep,
+    # 1 / Gamma for more rows than the workgroup has lanes; errors at and past 256 and at the last row
+    edge = (63, 64, 255, 256, 299)
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, edge, 5, pin=(257, 298, 0))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, range(256, 272), 0, note="-second")     # sixteen, all in the second step
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, range(0, 300, 19), 0, note="-spread")   # sixteen, in every wave of both steps
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, range(0, 300, 43), 4, pin=(299, 256))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, range(0, 300, 43), 5)                   # e' = 4: undecoded
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, (64, 256), "mixed")
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, (256, 64), "aimed")
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, tuple(range(3, 256, 16)) + (290,), 0)   # seventeen: over, the last one not kept
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, range(50, 250), 0)                      # two hundred
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, edge, 5, fill="random", pin=(257, 298, 0))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, edge, 5, fill="spoiled", pin=(257, 298, 0))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, (), 8, ok="ones", pin=(256, 299))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, (), 8, ok="null", pin=(256, 299))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, edge, 3, cap=2)                         # a lowered cap: three errors are refused
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, edge, 2, cap=2, pin=(257,))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 13, (63, 256), 5, pin=(299, 257))           # k + c = 16: the sealed feed's LDS coefficients
+    add("k3_wide-257", "k3_wide", 769, WIDE_257, 4, (0, 256), 1, pin=(255,))
+    add("k3_wide-257", "k3_wide", 769, WIDE_257, 4, (256,), 1, pin=(0,))
+    add("k3_wide-256", "k3_wide", 769, tuple(range(256)), 4, (255,), 1, pin=(254,))      # exactly one step
+    add("k3_wide-65", "k3_wide", 769, tuple(range(65)), 4, (63, 64), 1, pin=(62,))       # the first position of the second wave
+    add("k3_wide-64", "k3_wide", 769, tuple(range(64)), 4, (63,), 1, pin=(0,))           # exactly one wave
+    add("k3_wide", "k3_wide", 1, WIDE_300, 16, edge, 5, pin=(257, 298, 0))
+    add("k3_wide-257", "k3_wide", 1, WIDE_257, 4, (0, 256), 1, pin=(255,))
+    # steered modified syndromes: every family of reveal_decode_cases.families() in every wave
+    add("k3_62", "k3_62", 769, ALL8, 4, (2,), "steered", pin=(0, 3, 7))
+    add("k8_62", "k8_62", 805, K8_ALL, 16, (4, 8, 20), "steered", pin=tuple(range(1, 26, 2)))
+    add("k3_wide", "k3_wide", 769, WIDE_300, 16, (64, 256), "steered", pin=(0, 63, 65, 127, 128, 191, 192, 255, 257, 270, 280, 290, 298, 299))
+    return out, parent
 
 
-CASES = _cases()
+CASES, PARENT_CASES = _cases()
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
+NEW = tuple(c.name for c in CASES[PARENT_CASES:])                            # ... and these came with it
 E2E = "k3_62-c4-d764-f2-e1-zero"
 
 
@@ -181,6 +221,13 @@ def solve_batch(S, x, F, e, p, plant=None):
     return ("decoded" if E else "consistent"), E, list(zip(F, YF))
 
 
+@functools.lru_cache(maxsize=None)
+def _solved(S, scheme, indices, checks, F, e, plant):
+    """solve_batch, remembered: both policies, and every test that asks again, solve a batch once"""
+    T = vc.tables(scheme, indices, checks)
+    return solve_batch(list(S), T.x, list(F), e, T.p, plant)
+
+
 def brute_force(S, x, F, e, p):
     """the definition without T: every subset E of 0 .. e non-erased positions for which Y on E u F (non-zero on E) reproduces all
     c syndromes -> [(E as [(position, Y)], F as [(position, Y)])]  (small committees only)"""
@@ -205,6 +252,32 @@ def brute_force(S, x, F, e, p):
 Finish = collections.namedtuple("Finish", "out report verdicts errors erasures")
 PLANTS = ("gamma_reversed", "root_on_erased", "z_not_divided", "errors_not_removed", "one_erasure_skipped", "cap_from_c", "f_over_swapped",
           "padding_stored")
+# ... and faults of the setup kernel's compaction and of a position's width, which only a wide committee can notice
+# (tests/test_reveal_erasure_reach.py says which cases do):
+#   compaction_restarts  the erased positions of a later 256-step are numbered from the step's own start
+#   keeps_last_16        the kept list is filled from its first slot again in every step: a later step's positions overwrite
+#                        the earlier ones (f itself is counted right)
+#   position_mod_256     a located or erased position loses its high byte in blame and correction
+#   counts_kept_only     f is reported, and compared with the checks, as min(f, 16)
+GAP_PLANTS = ("compaction_restarts", "keeps_last_16", "position_mod_256", "counts_kept_only")
+
+
+def planted_erasures(F, checks, plant):
+    """-> (the erased positions the finish works with, f as reported, the overflow word) under a fault of GAP_PLANTS"""
+    F, f = list(F), len(F)
+    if plant == "compaction_restarts":
+        F = sorted({j % STEP for j in F})
+        f = len(F)
+    elif plant == "keeps_last_16":
+        kept = []
+        for step in sorted({j // STEP for j in F}):
+            here = [j for j in F if j // STEP == step]
+            kept = here + kept[len(here):]
+        F = sorted(kept)
+    elif plant == "counts_kept_only":
+        f = min(f, KEPT)
+        F = F[:f]
+    return F, f, f > checks
 
 
 def model_finish(case, rows, policy, plant=None):
@@ -215,7 +288,12 @@ def model_finish(case, rows, policy, plant=None):
     F = list(case.erased) if case.ok == "flags" else []
     f = len(F)
     over = f > c
+    if plant in GAP_PLANTS:
+        F, f, over = planted_erasures(F, c, plant)
+    low = (lambda i: i % 256) if plant == "position_mod_256" else (lambda i: i)
     e = cap_of(case)
+    if plant in GAP_PLANTS and not over:
+        e = min(case.cap, (c - len(F)) // 2) if case.cap else (c - len(F)) // 2
     if plant == "cap_from_c" and not over:
         e = min(case.cap, c // 2) if case.cap else c // 2
     B = batches(case)
@@ -229,7 +307,7 @@ def model_finish(case, rows, policy, plant=None):
         S = [sum(T.H[d][i] * sh[i] for i in range(n_rows)) % p for d in range(c)]
         verdict, E, YF = "clean", [], []
         if not over:
-            kind, E, YF = solve_batch(S, T.x, F, e, p, plant)
+            kind, E, YF = _solved(tuple(S), case.scheme, case.indices, c, tuple(F), e, plant)
             verdict = {"clean": "clean", "consistent": "consistent", "decoded": len(E), "undecoded": -1}[kind]
             if kind in ("decoded", "undecoded"):
                 bad += 1
@@ -242,12 +320,12 @@ def model_finish(case, rows, policy, plant=None):
                 most = max(most, nu)
                 hist[nu - 1] += 1
                 for i, _ in E:
-                    blame[i] += 1
+                    blame[low(i)] += 1
                 if policy == CORRECT:
                     corrected += 1
             if policy == CORRECT and kind in ("consistent", "decoded"):
                 fix = E + (YF[:-1] if plant == "one_erasure_skipped" else YF)
-                sec = [(sec[s] - sum(T.corr[s][i] * y for i, y in fix)) % p for s in range(k)]
+                sec = [(sec[s] - sum(T.corr[s][low(i)] * y for i, y in fix)) % p for s in range(k)]
         verdicts.append(verdict)
         errors.append(E)
         erasures.append(YF)
@@ -280,15 +358,20 @@ def build(name):
     rows = base.rows.copy()
     others = [i for i in range(pos) if i not in case.erased]
     order = [others[int(i)] for i in rng.permutation(len(others))]
+    if case.pin is not None:
+        assert not set(case.pin) & set(case.erased)
+        order = list(case.pin) + [i for i in order if i not in case.pin]
     e = cap_of(case)
-    if case.errors == "mixed":
+    if case.errors == "steered":
+        per = _steer(case, rows, B, rng)
+    elif case.errors == "mixed":
         per = [tuple(sorted(order[(b + j) % len(order)] for j in range({0: 0, 1: 0, 2: e, 3: e + 1}[b % 4]))) for b in range(B)]
     elif case.errors == "aimed":
-        per = [tuple(sorted(order[:2]))] * B
+        per = [tuple(sorted(order[:case.checks - len(case.erased)]))] * B
         _aim(case, rows, per[0], B, rng)
     else:
         per = [tuple(sorted(order[:case.errors]))] * B
-    for i in others if case.errors != "aimed" else ():
+    for i in others if case.errors not in ("aimed", "steered") else ():
         bs = np.array([b for b in range(B) if i in per[b]], dtype=np.int64)
         if bs.size:
             rows[i, bs] = vc._add(rows[i, bs], vc._errors(rng, p, bs.size), p)
@@ -306,20 +389,31 @@ def build(name):
     return Built(rows, base.clean_rows, base.want, base.row_len, B, per)
 
 
-def _aim(case, rows, pair, B, rng):
-    """errors on the two positions `pair` with Z_a x_a^d + Z_b x_b^d = W x_j^d, d = 0, 1, for the first erased position j"""
+def _aim(case, rows, at, B, rng):
+    """errors on the c - f positions `at` whose modified syndromes are W x_j^d, d < c - f - those of ONE error on the erased position
+    j: the first erased one (on a committee wider than one step of the setup kernel the last one, so that the refused root sits
+    past position 255)"""
     T = tables(case)
     p, x = T.p, T.x
-    a, b = pair
-    j = case.erased[0]
+    j = case.erased[0] if len(case.indices) <= STEP else case.erased[-1]
     g = gamma_of([x[q] for q in case.erased], p)
+    weight = {i: sum(g[m] * pow(x[i], m, p) for m in range(len(g))) % p for i in at}
     for batch in range(B):
         W = int(rng.integers(1, p))
-        Z = dc.solve([[1, 1], [x[a], x[b]]], [W, W * x[j] % p], p)
-        for i, z in zip(pair, Z):
-            G = sum(g[m] * pow(x[i], m, p) for m in range(len(g))) % p
-            err = z * pow(G, -1, p) * pow(T.u[i], -1, p) % p
-            rows[i, batch] = (int(rows[i, batch]) + err) % p
+        dc.steer(rows, T, at, batch, [W * pow(x[j], d, p) % p for d in range(len(at))], weight)
+
+
+def _steer(case, rows, B, rng):
+    """errors on the c - f pinned positions so that batch b's MODIFIED syndromes are those of family b mod F: the Vandermonde
+    system gives Z, the error is Z_i / (Gamma(x_i) u_i).  -> per batch, the positions whose error is not zero"""
+    T = tables(case)
+    p, n = T.p, case.checks - len(case.erased)
+    assert len(case.pin) == n >= 3
+    g = gamma_of([T.x[q] for q in case.erased], p)
+    weight = {i: sum(g[m] * pow(T.x[i], m, p) for m in range(len(g))) % p for i in case.pin}
+    z, fams = dc.no_point(T, rng), dc.families(n)
+    pts = [T.x[i] for i in case.pin]
+    return [dc.steer(rows, T, case.pin, b, dc.family_syndromes(fams[b % len(fams)], n, pts, z, cap_of(case), p, rng), weight) for b in range(B)]
 
 
 def refilled(name, fill):

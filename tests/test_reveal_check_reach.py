@@ -88,6 +88,14 @@ def test_shapes_sit_where_something_can_break():
     assert {c.checks for c in vc.CASES if c.scheme == "k3_62" and c.dim == 6301} == {1, 2, 4}
     assert all(1 <= c.checks <= min(vc.redundancy(c), vc.MAX_CHECKS) for c in vc.CASES)
     assert {c.feed for c in vc.CASES} == {"one", "descending"}
+    # the wide committee: its literals are extremes.omegas' (any distinct nodes), both coefficient paths, two workgroups and a tail
+    import extremes
+    p, k, t, n, w2, w3 = vc.SCHEMES["k3_wide"]
+    assert (w2, w3) == extremes.omegas(p, k, t, n) and p == vc.SCHEMES["k3_62"][0] and (k, t, n) == (3, 1, 300)
+    wide = [c for c in vc.CASES if c.scheme == "k3_wide"]
+    assert {vc.width(c) for c in wide} == {5, 16, 19} and {vc.coef_path(c) for c in wide} == {"lds", "global"}
+    assert {(len(c.indices), c.checks) for c in wide} >= {(300, 2), (300, 13), (300, 16), (257, 2)}
+    assert {vc.batches(c) for c in wide} == {1, 257} and 769 % 3 == 1
     # the any-int64 rows hold the extremes
     rows = vc.build("k3_62-c4-d1000-crafted").rows
     assert vc.I64_MIN in rows and vc.I64_MAX in rows
@@ -103,6 +111,63 @@ def test_two_faulty_rows_are_located_to_nobody():
         assert fin.report[0] == vc.batches(case) and fin.report[1] == 0, case.name
         seen.add(min(case.checks, 3))
     assert seen == {1, 2, 3}
+
+
+def test_wide_cases_blame_positions_past_a_byte():
+    """the faulty rows of the wide cases are pinned: at least two cases blame a position >= 256, one the last row of 300 and one the
+    last row of 257 - in the model's report, at the word the pinned position names"""
+    high, last = [], []
+    for case in vc.CASES:
+        if case.scheme != "k3_wide" or case.fault != "row":
+            continue
+        b = vc.build(case.name)
+        assert b.faulty == tuple(case.pin)
+        fin = vc.model_finish(case, b.rows, vc.CORRECT)
+        B = vc.batches(case)
+        assert fin.report[4:] == [B if i == b.faulty[0] else 0 for i in range(len(case.indices))], case.name
+        if b.faulty[0] >= 256:
+            high.append(case.name)
+        if b.faulty[0] == len(case.indices) - 1:
+            last.append(len(case.indices))
+    assert len(high) >= 2 and set(last) == {257, 300}, (high, last)
+    two = [vc.build(c.name).faulty for c in vc.CASES if c.scheme == "k3_wide" and c.fault == "two"]
+    assert all(max(f) >= 256 for f in two) and len(two) == 3
+
+
+def test_steered_geometric_syndromes():
+    """a ratio that is a point is located there; a ratio that is no point, and the ratio 1 - the node that is no row - are not"""
+    case = vc.BY_NAME["k3_62-c4-d769-steered"]
+    b, T = vc.build(case.name), vc.tables(case.scheme, case.indices, case.checks)
+    fin = vc.model_finish(case, b.rows, vc.CORRECT)
+    for batch in (0, 1, 2, 255, 256):
+        sh = [int(b.rows[i][batch]) % T.p for i in range(8)]
+        S = [sum(T.H[d][i] * sh[i] for i in range(8)) % T.p for d in range(4)]
+        ratio = S[1] * pow(S[0], -1, T.p) % T.p
+        assert all(S[d + 1] == ratio * S[d] % T.p for d in range(3)), "the planted errors do not give the syndromes back"
+        assert (ratio == T.x[case.pin[0]], ratio not in T.x + [1], ratio == 1) == tuple(batch % 3 == r for r in range(3))
+    assert fin.verdicts == [("located", "unlocated", "unlocated")[batch % 3] for batch in range(vc.batches(case))]
+    located = len(range(0, vc.batches(case), 3))
+    assert fin.report[:3] == [vc.batches(case), located, located] and fin.report[4 + case.pin[0]] == located
+    out = fin.out.reshape(-1)
+    want = b.want
+    good = np.array([batch % 3 == 0 for batch in range(vc.batches(case)) for _ in range(3)][:case.dim])
+    assert np.array_equal(out[good], want[good]) and (out[~good] != want[~good]).any()
+
+
+def test_a_lost_high_byte_is_noticed_by_the_wide_cases_alone():
+    """position_mod_256: a case of up to 256 rows cannot tell (a position below 256 is its own low byte: the model is not even
+    asked); of the older cases with more rows none locates a position past 255; the pinned wide cases do"""
+    noticed = {}
+    for case in vc.CASES:
+        if len(case.indices) <= 256:
+            continue
+        b = vc.build(case.name)
+        good, off = vc.model_finish(case, b.rows, vc.CORRECT), vc.model_finish(case, b.rows, vc.CORRECT, plant="position_mod_256")
+        noticed[case.name] = good.report != off.report or not np.array_equal(good.out, off.out)
+    old = [n for n, hit in noticed.items() if hit and vc.BY_NAME[n].scheme != "k3_wide"]
+    new = [n for n, hit in noticed.items() if hit and vc.BY_NAME[n].scheme == "k3_wide"]
+    print("position_mod_256 noticed by", new, "and of the older cases by", old)
+    assert not old and len(new) >= 3
 
 
 PLANTS = ("weight", "no_node1", "locate", "sign")

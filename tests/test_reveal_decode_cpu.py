@@ -145,3 +145,4 @@ def test_the_lane_decoder_on_the_cpu(built, tmp_path):
     print(run.stdout)
     assert run.returncode == 0, run.stdout[-2000:]
     assert run.stdout.count("decoded as planted") == 10 and "FAILURES" not in run.stdout
+    assert run.stdout.count("steered batches as constructed") == 10                       # ... and the steered families on every shape

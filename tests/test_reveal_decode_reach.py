@@ -2,7 +2,9 @@
 equals brute force over all subsets on every 8-row case), planted faults within the cap come back as exactly the planted positions
 with the other rows' reconstruction and the true secrets as output, the guaranteed band e + 1 .. c - e is undecoded in every batch,
 nu = 1 is reveal_check_cases' locate rule, the table reaches every nu, the S_0 = 0 branch, a Berlekamp-Massey length change at the
-last syndrome and a mixed wave, and every one of eight faults planted in the model is noticed by a case of the table."""
+last syndrome and a mixed wave, and every one of eight faults planted in the model is noticed by a case of the table.  The wide
+committee's cases blame positions past a byte, every steered family comes back as its construction says, and three more planted
+faults say what only those cases notice."""
 import numpy as np
 import pytest
 
@@ -129,6 +131,114 @@ def test_the_table_reaches_every_branch(built, finishes):
                  ("k8_62", 26, 8, 805), ("k8_62", 12, 2, 805), ("pss155", 260, 5, 1), ("pss155", 260, 4, 250)):
         assert want in shapes, want
     assert {dc.coef_path(c) for c in dc.CASES} == {"lds", "global"}
+    wide = [c for c in dc.CASES if c.scheme == "k3_wide"]
+    assert {dc.coef_path(c) for c in wide} == {"lds", "global"} and {(len(c.indices), c.checks) for c in wide} == {(300, 16), (300, 13), (257, 4)}
+    assert {c.dim for c in wide} == {1, 769} and any(c.feed == "descending" for c in wide)
+    assert {c.fault[1] for c in wide if isinstance(c.fault, tuple) and c.checks == 16 and c.dim == 769} == set(range(1, 11))
+    assert {c.fault for c in wide if isinstance(c.fault, str)} >= {"stair", "first", "last", "s0zero", "steered"}
+    assert {c.values for c in wide} == {"sums", "crafted", "congruent"}
+
+
+def test_wide_cases_blame_positions_past_a_byte(built, finishes):
+    """from Built.faulty: at least two wide cases are decoded with a position >= 256, one with the last row of 300 and one with the
+    last row of 257 - and the model blames exactly those words"""
+    high, last = [], set()
+    for name in dc.NEW:
+        case, b, fin = dc.BY_NAME[name], dc.build(name), finishes[name]
+        if case.scheme != "k3_wide" or not isinstance(case.fault, tuple) or case.fault[1] > dc.cap_of(case):
+            continue
+        at = b.faulty[0]
+        assert set(case.pin or ()) <= set(at) or len(case.pin) > len(at)
+        assert fin.report[dc.HEAD:] == [b.batches if i in at else 0 for i in range(len(case.indices))], name
+        if max(at) >= 256:
+            high.append(name)
+        if max(at) == len(case.indices) - 1:
+            last.add(len(case.indices))
+    print("decoded with a position >= 256:", high)
+    assert len(high) >= 2 and last == {257, 300}
+    stair = finishes["k3_wide-c16-d769-stair"]
+    assert any(stair.report[dc.HEAD + 256:]) and any(stair.report[dc.HEAD:dc.HEAD + 64])
+
+
+STEERED = [n for n in dc.NEW if dc.BY_NAME[n].fault == "steered"]
+
+
+@pytest.mark.parametrize("name", STEERED)
+def test_steered_families_have_their_verdicts(built, finishes, name):
+    """the planted errors give the family's syndromes back exactly, and every batch comes back as its family's construction says;
+    where the definition promises nothing the model was asked, and what it said is written down here"""
+    case, b, fin = dc.BY_NAME[name], dc.build(name), finishes[name]
+    T, e, n = dc.tables(case), dc.cap_of(case), case.checks
+    fams = dc.families(n)
+    asked = {"s0_forced_zero": -1, "cap_plus_one": -1, "cap_minus_one_and_z": -1}
+    seen = {}
+    for batch in range(b.batches):
+        fam = fams[batch % len(fams)]
+        S = _syndromes(case, b.rows, batch)
+        if fam == "ratio_z":
+            assert S[0] and all(S[d + 1] * S[0] % T.p == S[1] * S[d] % T.p for d in range(n - 1)) and S[1] * pow(S[0], -1, T.p) % T.p not in T.x + [0, 1]
+        elif fam in ("ratio_one", "all_pm1"):
+            assert len(set(S)) == 1 and S[0] and (fam == "ratio_one" or S[0] == T.p - 1)
+        elif fam == "ratio_zero":
+            assert S[0] and not any(S[1:])
+        elif fam == "late_jump":
+            assert S[-1] and not any(S[:-1])
+        elif fam == "zero_half":
+            assert not any(S[:n // 2]) and all(S[n // 2:])
+        elif fam in ("two_points_cancel", "s0_zero_two_points", "s0_forced_zero", "double_root"):
+            assert S[0] == 0 and any(S)
+        want = dc.family_verdict(fam, n, e, case.pin)
+        got = fin.verdicts[batch]
+        if want is None:
+            assert got == asked[fam], (batch, fam, got)
+        else:
+            assert got == want[0], (batch, fam, got, want)
+            if got > 0:
+                assert tuple(i for i, _ in fin.errors[batch]) == want[1] == b.faulty[batch], (batch, fam)
+        seen.setdefault(fam, got)
+    assert set(seen) == set(fams) and b.batches >= 4 * len(fams)                   # every family, in every wave
+    print(name, seen)
+    if name == "k3_62-c4-d769-steered":                                            # the eleven first families on the 8-row shape
+        assert [seen[f] for f in dc.FAMILIES[:8]] == [-1] * 8
+        assert [fin.errors[8 + j] and [i for i, _ in fin.errors[8 + j]] for j in range(3)] == [[7], [0, 7], [3, 5]]
+    if case.cap:
+        assert seen["three_points"] == -1 and seen["cap_points"] == case.cap
+    elif n >= 8:
+        assert seen["three_points"] == 3 and seen["cap_points"] == n // 2
+
+
+def _decodes(case, plant):
+    """per batch, what the model's decoder says under `plant` - all a fault of GAP_PLANTS' root search can change"""
+    b = dc.build(case.name)
+    return [dc._decoded(tuple(S), case.scheme, case.indices, case.checks, dc.cap_of(case), plant) if any(S) else None
+            for S in (_syndromes(case, b.rows, batch) for batch in range(b.batches))]
+
+
+@pytest.mark.parametrize("plant", dc.GAP_PLANTS)
+def test_what_only_the_new_cases_notice(built, finishes, plant):
+    """position_mod_256 is noticed by wide cases and by no older case (up to 256 rows a position is its own low byte; the older
+    260-row cases are asked).  A root search that also tries the node 1, or 0, is noticed by steered cases; whether an older case
+    notices is found out and printed, batch by batch of the whole older table."""
+    old, new = [], []
+    for case in dc.CASES:
+        if plant == "position_mod_256":
+            if len(case.indices) <= 256:
+                continue
+            b = dc.build(case.name)
+            wrong = dc.model_finish(case, b.rows, dc.CORRECT, plant=plant)
+            hit = wrong.report != finishes[case.name].report or not np.array_equal(wrong.out, finishes[case.name].out)
+        else:
+            if case.name in dc.NEW and case.fault != "steered":
+                continue
+            hit = _decodes(case, plant) != _decodes(case, None)
+        if hit:
+            (new if case.name in dc.NEW else old).append(case.name)
+    print(f"planted {plant}: noticed by {len(new)} new cases {new[:6]} and by {len(old)} older cases {old[:6]}")
+    assert new, plant
+    if plant == "position_mod_256":
+        assert not old
+    else:
+        assert not old, "an older case notices after all: say so in the table's comment"
 
 
 @pytest.mark.parametrize("plant", dc.PLANTS)

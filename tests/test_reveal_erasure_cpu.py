@@ -146,3 +146,4 @@ def test_the_erasure_steps_on_the_cpu(built, tmp_path, flags):
     print(run.stdout, run.stderr[-2000:])
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
     assert run.stdout.count("repaired as planted") == 9 and "FAILURES" not in run.stdout and "runtime error" not in run.stderr
+    assert run.stdout.count("steered batches undecoded as constructed") == 9             # ... and the steered families on every shape

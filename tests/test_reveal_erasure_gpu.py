@@ -3,7 +3,8 @@ crypto.reveal_sealed_repaired.  Every case of tests/reveal_erasure_cases.py is f
 under both policies; output, every report word and the sentinels past both buffers are bit-exact against the Python-integer model
 (proven to be the definition by tests/test_reveal_erasure_reach.py).  Then: without erasures the call is finish_decoded_dev on a
 twin job; what an erased row added does not matter; the refusals and their order; the host form; and sealed clerking results with
-one and with f = c tampered boxes, whose d_ok words reach the finish untouched.  No test provokes a fault: a refused box is an
+one and with f = c tampered boxes, whose d_ok words reach the finish untouched - and, on the 300-row committee, boxes 63 and 256
+refused in two update calls.  No test provokes a fault: a refused box is an
 ordinary status."""
 import numpy as np
 import pytest
@@ -94,7 +95,8 @@ def test_without_erasures_it_is_the_decoding_finish(gpu, name):
 
 
 # ---- 3. whatever an erased row added -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["k3_62-c4-d764-f2-e1-zero", "k3_62-c4-d764-f2-e1-spoiled", "k3_62-c1-d764-f1-e0-zero", "k8_62-c16-d805-f8-e4-random"])
+@pytest.mark.parametrize("name", ["k3_62-c4-d764-f2-e1-zero", "k3_62-c4-d764-f2-e1-spoiled", "k3_62-c1-d764-f1-e0-zero", "k8_62-c16-d805-f8-e4-random",
+                                  "k3_wide-c16-d769-f5-e5-zero"])
 def test_what_an_erased_row_added_does_not_matter(gpu, name):
     """a position refused (it added nothing) and the same position fed with random values: identical d_out and report"""
     case = ec.BY_NAME[name]
@@ -188,7 +190,7 @@ def test_refusals_are_the_decoding_finishs_and_leave_the_job_usable(gpu):
 
 # ---- 5. the host form ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", [ec.E2E, "k3_62-c4-d764-f4-e0-zero", "k3_62-c4-d764-f5-e0-zero", "k3_62-c1-d764-f1-e0-zero",
-                                  "k8_62-c16-d805-f8-e4-random", "k3_62-c4-d764-f0-e2-zero-null"])
+                                  "k8_62-c16-d805-f8-e4-random", "k3_62-c4-d764-f0-e2-zero-null", "k3_wide-c13-d769-f2-e5-zero"])
 def test_reconstruct_erasures_host_form(gpu, name):
     from sda_amd import crypto
     case, b = ec.BY_NAME[name], ec.build(name)
@@ -221,22 +223,30 @@ def _boxes(rows, pk, liars, seed):
 
 @pytest.mark.parametrize("name,liars", [("k3_62-c4-d764-f0-e0-zero-ones", (5,)), ("k3_62-c4-d764-f0-e0-zero-ones", (0, 2, 6, 7)),
                                         ("k8_62-c16-d805-f0-e3-zero-ones", (11,)),
-                                        ("k8_62-c16-d805-f0-e3-zero-ones", tuple(range(1, 26, 2))[:13] + (0, 2, 4))])
+                                        ("k8_62-c16-d805-f0-e3-zero-ones", tuple(range(1, 26, 2))[:13] + (0, 2, 4)),
+                                        ("k3_wide-c13-d769-f2-e5-zero", (63, 256))])
 def test_refused_boxes_are_repaired_from_the_sealed_updates_own_flags(gpu, name, liars):
     """update_sealed_rows_dev refuses the tampered boxes (an ordinary status: bit 16, d_ok[r] = 0); the d_ok array goes to
     finish_erasures_dev as the update left it, and the output is reconstruct() of the other rows.  On config 4's committee the three
-    faulty rows of the case are only decodable next to ONE refused box; with f = c = 16 they are taken on trust"""
+    faulty rows of the case are only decodable next to ONE refused box; with f = c = 16 they are taken on trust.  The wide
+    committee's 300 boxes go in two calls - d_ok is written at two offsets - and its refused boxes are the case's own erased
+    positions, 63 and 256, next to five faulty rows"""
     from sda_amd import crypto
     case = ec.BY_NAME[name]
     b = ec.build(name)
     rows = b.rows if len(liars) < case.checks else b.clean_rows
-    assert len(liars) in (1, case.checks)
+    assert len(liars) in (1, case.checks) or liars == case.erased
     pk, sk = _keys(61)
     job = upload_boxes(_boxes(rows, pk, liars, 62))
     rec = crypto.SecretReconstructor(scheme_of(case), case.dim)
     f = Feeder(rec, rows, job, pk, sk)
     rec.begin_checked_dev(case.indices, f.pos, f.row_len, case.checks)
-    f.feed("one")
+    if f.pos <= 256:
+        f.feed("one")
+    else:                                                                 # the wide committee: the second half first
+        half = f.pos // 2
+        f.sealed(half, f.pos - half)
+        f.sealed(0, half)
     before = u32(f.d_ok, f.pos)
     from sda_amd.device import DeviceBuffer
     d_out = DeviceBuffer.from_numpy(np.full(case.dim + 8, SENTINEL, dtype=np.int64))

@@ -2,7 +2,9 @@
 force over all error subsets, with F fixed, on every 8-row case), with F empty it is reveal_decode_cases' model on that module's
 whole table, corrected output within the guarantees is the C oracle's reconstruct of the surviving rows, an erased row's content
 does not matter, the table reaches every (f, nu) class by name, and every one of eight faults planted in the model is noticed by a
-case of the table."""
+case of the table.  The wide committee's cases reach the setup kernel's second step, every wave of a step and the positions it counts
+and does not keep; every steered family comes back as its construction says; four more planted faults say what only those cases
+notice."""
 import numpy as np
 import pytest
 
@@ -129,11 +131,12 @@ def test_the_table_reaches_every_class(built, finishes):
         v = finishes[name].verdicts[:64]
         assert {"clean", "consistent", -1} <= set(v) and any(isinstance(q, int) and q > 0 for q in v), name
     # the aimed errors: the modified syndromes are one error's on an erased position, and nothing is decoded
-    aimed = ec.BY_NAME["k3_62-c4-d764-f2-eaimed-zero"]
-    b, T = ec.build(aimed.name), ec.tables(aimed)
-    S = _syndromes(aimed, b.rows, 0)
-    Tm = ec.modified(S, ec.gamma_of([T.x[j] for j in aimed.erased], T.p), T.p)
-    assert Tm[0] and Tm[1] == Tm[0] * T.x[aimed.erased[0]] % T.p and set(finishes[aimed.name].verdicts) == {-1}
+    for aimed, at in ((ec.BY_NAME["k3_62-c4-d764-f2-eaimed-zero"], 2), (ec.BY_NAME["k3_wide-c16-d769-f2-eaimed-zero"], 256)):
+        b, T = ec.build(aimed.name), ec.tables(aimed)
+        S = _syndromes(aimed, b.rows, 0)
+        Tm = ec.modified(S, ec.gamma_of([T.x[j] for j in aimed.erased], T.p), T.p)
+        assert at in aimed.erased and Tm[0] and all(Tm[d + 1] == Tm[d] * T.x[at] % T.p for d in range(len(Tm) - 1))
+        assert set(finishes[aimed.name].verdicts) == {-1}
     # an error planted on an erased position is absorbed, not counted
     spoiled = finishes["k3_62-c4-d764-f2-e1-spoiled"]
     assert spoiled.report[:3] == finishes["k3_62-c4-d764-f2-e1-zero"].report[:3] and spoiled.report[5] == 1
@@ -141,6 +144,98 @@ def test_the_table_reaches_every_class(built, finishes):
     assert any(0 in c.erased for c in ec.CASES) and any(len(c.indices) - 1 in c.erased for c in ec.CASES)
     B = {ec.batches(c) for c in ec.CASES if c.scheme == "k3_62"}
     assert {1, 255, 256, 257} <= B and {c.dim % 3 for c in ec.CASES if c.scheme == "k3_62"} == {0, 1, 2}
+
+
+def test_the_wide_cases_reach_the_setup_kernels_steps_and_waves(built, finishes):
+    """what reveal_erasure_setup_kernel does per 256 positions and per wave of 64, read off the tables' erased sets"""
+    wide = [c for c in ec.CASES if c.scheme == "k3_wide" and c.ok == "flags"]
+    steps = lambda c: {j // ec.STEP for j in c.erased}
+    waves = lambda c, step: {j % ec.STEP // 64 for j in c.erased if j // ec.STEP == step}
+    assert any(steps(c) == {0, 1} for c in wide) and any(steps(c) == {1} for c in wide)                    # the count is carried; a step adds nothing
+    assert any(waves(c, 0) == {0, 1, 2, 3} for c in wide), "no case with erased positions in all four waves of a step"
+    assert any(len(c.erased) <= ec.KEPT and max(c.erased) >= 256 and min(c.erased) < 256 for c in wide)    # a kept position >= 256 behind earlier ones
+    assert any(len(c.erased) == ec.KEPT and min(c.erased) >= 256 for c in wide)                            # all sixteen slots from the second step
+    over = [c for c in wide if len(c.erased) > ec.KEPT]
+    assert {len(c.erased) for c in over} == {17, 200}
+    seventeen = next(c for c in over if len(c.erased) == 17)
+    assert sorted(seventeen.erased)[15] < 256 <= sorted(seventeen.erased)[16]                              # counted, not kept
+    for c in over:
+        assert finishes[c.name].report[:8] == [0, 0, 0, ec.NONE64, ec.NONE64, 0, len(c.erased), 1] and set(finishes[c.name].verdicts) == {"clean"}
+    assert {len(c.indices) for c in ec.CASES if c.scheme == "k3_wide"} == {64, 65, 256, 257, 300}          # a wave, + 1, a step, + 1, > kThreads
+    assert {vc.coef_path(c) for c in wide} == {"lds", "global"} and {c.dim for c in wide} == {1, 769}
+    assert {c.fill for c in wide} >= {"zero", "random", "spoiled"} and any(c.cap for c in wide)
+    assert {c.ok for c in ec.CASES if c.scheme == "k3_wide"} == {"flags", "ones", "null"}
+    import extremes
+    p, k, t, n, w2, w3 = ec.SCHEMES["k3_wide"]
+    assert (w2, w3) == extremes.omegas(p, k, t, n)
+    # errors past a byte: at least two wide cases are decoded with a position >= 256, one with the last row
+    high, last = [], []
+    for c in ec.CASES:
+        b = ec.build(c.name)
+        if c.scheme != "k3_wide" or not isinstance(c.errors, int) or not 0 < c.errors <= ec.cap_of(c) or len(c.erased) > c.checks:
+            continue
+        at = b.faulty[0]
+        assert finishes[c.name].report[ec.HEAD:] == [b.batches if i in at else 0 for i in range(len(c.indices))], c.name
+        high += [c.name] if max(at) >= 256 else []
+        last += [c.name] if max(at) == len(c.indices) - 1 else []
+    print("decoded with a position >= 256:", high, "with the last row:", last)
+    assert len(high) >= 2 and last
+
+
+@pytest.mark.parametrize("name", [n for n in ec.NEW if ec.BY_NAME[n].errors == "steered"])
+def test_steered_families_have_their_verdicts(built, finishes, name):
+    """the planted errors give the family's MODIFIED syndromes back exactly - whatever the erased rows hold - and every batch comes
+    back as its family's construction says; where the definition promises nothing the model was asked"""
+    case, b, fin = ec.BY_NAME[name], ec.build(name), finishes[name]
+    T, e, n = ec.tables(case), ec.cap_of(case), case.checks - len(case.erased)
+    fams = dc.families(n)
+    g = ec.gamma_of([T.x[j] for j in case.erased], T.p)
+    seen = {}
+    for batch in range(b.batches):
+        fam = fams[batch % len(fams)]
+        Tm = ec.modified(_syndromes(case, b.rows, batch), g, T.p)
+        assert len(Tm) == n and Tm == ec.modified(_syndromes(case, ec.refilled(name, "random"), batch), g, T.p)
+        if fam == "ratio_one":
+            assert len(set(Tm)) == 1 and Tm[0]
+        elif fam == "all_pm1":
+            assert Tm == [T.p - 1] * n
+        elif fam == "late_jump":
+            assert Tm[-1] and not any(Tm[:-1])
+        elif fam == "ratio_zero":
+            assert Tm[0] and not any(Tm[1:])
+        want = dc.family_verdict(fam, n, e, case.pin)
+        got = fin.verdicts[batch]
+        if want is None:
+            assert got == -1, (batch, fam, got)
+        else:
+            assert got == want[0], (batch, fam, got, want)
+            if got != -1:
+                assert tuple(sorted(i for i, _ in fin.errors[batch])) == want[1] == b.faulty[batch], (batch, fam)
+        seen.setdefault(fam, got)
+    assert set(seen) == set(fams) and b.batches >= 4 * len(fams)
+    print(name, "n", n, "cap", e, seen)
+
+
+@pytest.mark.parametrize("plant", ec.GAP_PLANTS)
+def test_what_only_the_new_cases_notice(built, finishes, plant):
+    """the faults of the compaction and of a position's width.  A case whose erased set the fault leaves as it is, on a committee of
+    up to 256 rows, cannot tell - the model is not even asked; every other case is.  compaction_restarts, keeps_last_16 and
+    position_mod_256 are noticed by wide cases and by no older case; which older cases notice counts_kept_only is printed."""
+    old, new = [], []
+    for case in ec.CASES:
+        F = list(case.erased) if case.ok == "flags" else []
+        if ec.planted_erasures(F, case.checks, plant) == (F, len(F), len(F) > case.checks) and (plant != "position_mod_256" or len(case.indices) <= 256):
+            continue
+        b = ec.build(case.name)
+        right, wrong = finishes[case.name], ec.model_finish(case, b.rows, ec.CORRECT, plant=plant)
+        if wrong.report != right.report or not np.array_equal(wrong.out, right.out):
+            (new if case.name in ec.NEW else old).append(case.name)
+    print(f"planted {plant}: noticed by {len(new)} new cases {new[:8]} and by {len(old)} older cases {old}")
+    assert new, plant
+    if plant == "counts_kept_only":
+        assert old == ["k8_62-c16-d805-f17-e0-zero"]
+    else:
+        assert not old
 
 
 @pytest.mark.parametrize("plant", ec.PLANTS)
