@@ -703,6 +703,49 @@ int sda_secret_unmasker_unmask_jobs_dev(sda_secret_unmasker_t* u, sda_mask_combi
                                         const uint32_t* d_status_masks, const uint32_t* d_status_results, int64_t* d_out,
                                         size_t out_cap, void* stream);
 
+/* The same last step for a CHECKED job (sda_secret_reconstructor_begin_checked_dev, every position fed), in one call:
+ * sda_secret_unmasker_unmask_jobs_dev keeps refusing checked jobs, this is the entry point that takes them.  `end` names the
+ * finish whose verdicts are wanted - SDA_CHECKED_END_LOCATE: finish_checked_dev, SDA_CHECKED_END_DECODE: finish_decoded_dev,
+ * SDA_CHECKED_END_ERASURES: finish_erasures_dev - and max_errors, policy, d_ok and d_report are that finish's arguments
+ * (max_errors is not read for LOCATE; d_ok is read for ERASURES only, NULL: nothing erased).  `c` is a mask combiner job of
+ * dimension L = r's dimension, as for unmask_jobs_dev; NULL, or a None combiner, under SDA_MASKING_NONE.  The call ends both jobs.
+ *   THE RESULT.  With v[i] = what the named finish stores at d_out[i] under the same policy - the correction is applied under
+ * the sharing modulus first - d_out[i] = (canonical(v[i], q_mask) - fold(mask sum[i], q_mask)) mod q_mask, i < L: bit for bit
+ * the chain finish_*_dev -> d_masked, sda_mask_combiner_finish_dev -> d_mask, sda_secret_unmasker_unmask_dev, with moduli that
+ * may differ (full.rs:60-63, chacha.rs:86-89).  None: d_out = v.  ChaCha with no seed fed: the mask is zero.  The padding of the
+ * last batch is checked like any batch and not stored (batched.rs:94), and no mask sum at or beyond L is read.  d_report holds
+ * the words the named finish gives for the same job, bit for bit (sda_reconstruct_report_words(n_rows) words for LOCATE,
+ * sda_reconstruct_decode_report_words(n_rows) for the other two), WHETHER OR NOT THE GATE IS SHUT.
+ *   THE GATE: d_status_masks / d_status_results are optional device words, the d_status of the jobs' sealed updates; they may be
+ * the same word.  NOTHING is stored to d_out when *d_status_masks != 0 or (*d_status_results & ~results_pass_bits) != 0 when the
+ * kernel runs (sodium.rs:78-80).  results_pass_bits is 0, or 16 for the caller who repairs refused boxes as erasures: bit 16 of the
+ * results' word then does not shut the gate, every other bit still does.  The call's status does not tell; the jobs are ended
+ * either way.
+ *   COST: one kernel for LOCATE and DECODE, two for ERASURES (the setup kernel of finish_erasures_dev, then the finish); neither
+ * the masked output nor the combined mask is written to device memory.  NO SYNCHRONISATION AND NO COPY TO THE HOST; nothing is
+ * allocated beyond the erasure table scratch finish_erasures_dev reserves.  L == 0 is SDA_OK: the report is initialised, nothing
+ * is launched, both jobs are ended.  d_out needs 8-byte alignment only.
+ *   REFUSALS, all before any launch, both jobs left as they were, IN THIS ORDER:
+ *     1. those of unmask_jobs_dev that precede its test for a checked job, with its texts: NULL u or r, NULL c with a kind other
+ *        than None, u and c built from different masking schemes, the handles not on one device -> SDA_ERR_INVALID_ARGUMENT; the
+ *        reconstructor's job not begun -> SDA_ERR_STATE;
+ *     2. an unknown `end` -> SDA_ERR_INVALID_ARGUMENT;
+ *     3. those of the named finish, in its order, with its codes and texts: a plain job (begin_dev) -> SDA_ERR_STATE; a position
+ *        not fed -> SDA_ERR_STATE; DECODE on a job with one check, max_errors > floor(checks / 2) (DECODE, ERASURES), an unknown
+ *        policy, NULL d_out with L > 0, out_cap < L, NULL d_report -> SDA_ERR_INVALID_ARGUMENT;
+ *     4. the mask job not begun -> SDA_ERR_STATE;
+ *     5. SDA_VALUES_RUST_SIGNED on the unmasker or read into either job -> SDA_ERR_UNSUPPORTED;
+ *     6. Full / ChaCha with a mask job dimension other than L -> SDA_ERR_ASSERTION (full.rs:58, chacha.rs:83);
+ *     7. results_pass_bits other than 0 and 16 -> SDA_ERR_INVALID_ARGUMENT. */
+#define SDA_CHECKED_END_LOCATE   0   /* finish_checked_dev's end  */
+#define SDA_CHECKED_END_DECODE   1   /* finish_decoded_dev's end  */
+#define SDA_CHECKED_END_ERASURES 2   /* finish_erasures_dev's end */
+int sda_secret_unmasker_unmask_checked_jobs_dev(sda_secret_unmasker_t* u, sda_mask_combiner_t* c, sda_secret_reconstructor_t* r,
+                                                int end, const uint32_t* d_ok, unsigned max_errors, int policy,
+                                                const uint32_t* d_status_masks, const uint32_t* d_status_results,
+                                                uint32_t results_pass_bits, int64_t* d_out, size_t out_cap, uint64_t* d_report,
+                                                void* stream);
+
 /* RecipientOutput::positive - client/src/receive.rs:13-21: v < 0 ? v + modulus : v.  Host-side,
  * element-wise; the identity on this library's canonical outputs. */
 int sda_positive(const int64_t* values, size_t len, int64_t modulus, int64_t* out);

@@ -47,6 +47,7 @@ SHARING_ADDITIVE, SHARING_PACKED_SHAMIR = 0, 1
 MASKING_NONE, MASKING_FULL, MASKING_CHACHA = 0, 1, 2
 CHECK_REPORT, CHECK_CORRECT = 0, 1        # the policies of sda_secret_reconstructor_finish_checked_dev
 RECONSTRUCT_MAX_CHECKS = 16
+CHECKED_END_LOCATE, CHECKED_END_DECODE, CHECKED_END_ERASURES = 0, 1, 2    # the ends of sda_secret_unmasker_unmask_checked_jobs_dev
 
 
 class SharingScheme(C.Structure):
@@ -171,6 +172,8 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sda_secret_unmasker_unmask_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_secret_unmasker_unmask_jobs_dev": (C.c_int, [_H, _H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sda_secret_unmasker_unmask_checked_jobs_dev": (C.c_int, [_H, _H, _H, C.c_int, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_void_p,
+                                                              C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sda_varint_slot_size": (C.c_size_t, [C.c_size_t]),
     "sda_varint_encode_rows_dev": (C.c_int, [_H, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p]),

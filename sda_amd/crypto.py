@@ -856,6 +856,20 @@ class SecretUnmasker(_Handle):
             self._h, combiner._h if combiner is not None else None, reconstructor._h if reconstructor is not None else None,
             d_status_masks or None, d_status_results or None, d_out or None, out_cap, stream or None))
 
+    def unmask_checked_jobs_dev(self, combiner: Optional["MaskCombiner"], reconstructor: "SecretReconstructor", end: int, d_out: int,
+                                out_cap: int, d_report: int, d_ok: int = 0, max_errors: int = 0, correct: bool = False,
+                                d_status_masks: int = 0, d_status_results: int = 0, results_pass_bits: int = 0, stream: int = 0) -> None:
+        """unmask_jobs_dev for a CHECKED reconstructor job: end (capi.CHECKED_END_LOCATE / _DECODE / _ERASURES) names the finish -
+        finish_checked_dev, finish_decoded_dev, finish_erasures_dev - whose verdicts and report (d_report, that finish's words) are
+        wanted; d_out is that finish's output unmasked, from one kernel, with neither the masked output nor the combined mask in
+        HBM.  Ends both jobs.  d_ok: the erasure end's flags; max_errors as for the named finish.  The gate: *d_status_masks != 0
+        or (*d_status_results & ~results_pass_bits) != 0 when the kernel runs and nothing is stored to d_out - the report is
+        written all the same; results_pass_bits is 0, or 16 for the caller who repairs refused boxes"""
+        _check_mask(self._lib.sda_secret_unmasker_unmask_checked_jobs_dev(
+            self._h, combiner._h if combiner is not None else None, reconstructor._h if reconstructor is not None else None, end,
+            d_ok or None, max_errors, capi.CHECK_CORRECT if correct else capi.CHECK_REPORT, d_status_masks or None,
+            d_status_results or None, results_pass_bits, d_out or None, out_cap, d_report or None, stream or None))
+
 
 # ---- factory (client/src/crypto/mod.rs:58-66) ---------------------------------------------------------------
 class CryptoModule:
@@ -1027,8 +1041,8 @@ def reveal_sealed(aggregation: Aggregation, mask_job, result_job, indices: Optio
 def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
                           recipient_sk: bytes, checks: Optional[int] = None, correct: bool = False):
     """reveal_sealed for a packed sharing scheme with the clerking results checked against each other: the results' job carries
-    `checks` parity columns (None: min(n_rows - (t + k), 4)), and the reveal is the chain MaskCombiner.finish_dev +
-    SecretReconstructor.finish_checked_dev + SecretUnmasker.unmask_dev - the one-kernel unmask_jobs_dev reads a plain job only.
+    `checks` parity columns (None: min(n_rows - (t + k), 4)), and the reveal ends in SecretUnmasker.unmask_checked_jobs_dev with
+    finish_checked_dev's end - one kernel over both jobs' sums, both status words as its gates.
     Returns (RecipientOutput, RevealCheck); correct=True repairs every batch that one clerking result alone spoils.  The failures of
     reveal_sealed stay: a bad box fails the reveal whatever the check says (sodium.rs:78-80)."""
     return _reveal_sealed_with_checks(RevealCheck, "reveal_sealed_checked", aggregation, mask_job, result_job, indices, recipient_pk,
@@ -1037,7 +1051,7 @@ def reveal_sealed_checked(aggregation: Aggregation, mask_job, result_job, indice
 
 def reveal_sealed_decoded(aggregation: Aggregation, mask_job, result_job, indices: Sequence[int], recipient_pk: bytes,
                           recipient_sk: bytes, checks: Optional[int] = None, max_errors: int = 0, correct: bool = False):
-    """reveal_sealed_checked with SecretReconstructor.finish_decoded_dev in the chain: up to max_errors (0: floor(checks / 2))
+    """reveal_sealed_checked with finish_decoded_dev's end: up to max_errors (0: floor(checks / 2))
     disagreeing clerking results per batch are named and, with correct=True, repaired.  Returns (RecipientOutput, RevealDecode).
     A bad box still fails the reveal (sodium.rs:78-80)."""
     return _reveal_sealed_with_checks(RevealDecode, "reveal_sealed_decoded", aggregation, mask_job, result_job, indices, recipient_pk,
@@ -1058,49 +1072,20 @@ def reveal_sealed_repaired(aggregation: Aggregation, mask_job, result_job, indic
                            recipient_sk: bytes, checks: Optional[int] = None, max_errors: int = 0, correct: bool = True) -> RevealRepair:
     """reveal_sealed_decoded that REPAIRS refused clerking results instead of failing on them - the deliberate alternative to the
     reference's rule (sodium.rs:78-80), for a caller who prefers the other clerks' answer to none.  The sealed update's d_ok words
-    go to SecretReconstructor.finish_erasures_dev untouched and unread: a refused box is an erasure and costs one check, not two.
+    go to finish_erasures_dev's end of SecretUnmasker.unmask_checked_jobs_dev untouched and unread: a refused box is an erasure and
+    costs one check, not two; bit 16 of the results' status word does not shut that call's gate.
     The status word of the clerking results is RETURNED, not raised, for its bit 16; every other failure - a bad mask box, a wrong
     dimension, a malformed stream - fails the reveal as in reveal_sealed."""
-    from .device import DeviceBuffer
-    a = aggregation
-    sch, msch = a.committee_sharing_scheme, a.masking_scheme
-    masks, results = _parse_reveal_jobs("reveal_sealed_repaired", msch, mask_job, result_job, recipient_pk, recipient_sk)
-    if isinstance(sch, Additive):
-        raise SdaError(capi.ERR_UNSUPPORTED, "additive sharing has no redundancy to check")
-    rows = results.layout.rows
-    _check_result_indices(indices, rows, optional=False)
-    reconstructor = SecretReconstructor(sch, a.vector_dimension)
-    row_len, n_out = reconstructor._sealed_job_shape(None)
-    checks = reconstructor.default_checks(rows) if checks is None else checks
-    unmasker = SecretUnmasker(msch)
-    combiner = MaskCombiner(msch) if masks is not None else None
-    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the masked output, the
-    # combined mask, the output and the rows' ok words (two 32-bit words per entry)
-    cap = max(n_out, 1)
-    words = RevealDecode.HEAD + rows
-    d_buf = DeviceBuffer(2 + words + 3 * cap + (rows + 1) // 2).zero()
-    d_masked, d_mask, d_out, d_ok = (d_buf.at(2 + words + i * cap) for i in range(4))
-    held = []
-    if combiner is not None:
-        held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
-        combiner.finish_dev(d_mask, n_out)
-    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks, d_ok=d_ok))
-    reconstructor.finish_erasures_dev(d_ok, d_masked, n_out, d_buf.at(2), max_errors, correct)
-    unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
-    back = d_buf.to_numpy()
-    del held
-    status = int(back[1]) & 0xFFFFFFFF
-    _raise_sealed_status(int(back[0]) | (status & ~16))
-    report = back[2:2 + words].view(np.uint64).tolist()
-    first = 2 + words + 2 * cap
-    return RevealRepair(RecipientOutput(a.modulus, back[first:first + n_out].copy()), RevealDecode.from_words(report), status,
-                        int(report[6]), bool(report[7]))
+    output, report, status = _reveal_sealed_with_checks(RevealDecode, "reveal_sealed_repaired", aggregation, mask_job, result_job, indices,
+                                                        recipient_pk, recipient_sk, checks, max_errors, correct, repair=True)
+    return RevealRepair(output, RevealDecode.from_words(report), status, int(report[6]), bool(report[7]))
 
 
 def _reveal_sealed_with_checks(kind, name: str, aggregation: Aggregation, mask_job, result_job, indices, recipient_pk: bytes,
-                               recipient_sk: bytes, checks: Optional[int], max_errors: int, correct: bool):
-    """the chain of reveal_sealed_checked (kind RevealCheck: finish_checked_dev, max_errors is not read) and reveal_sealed_decoded
-    (RevealDecode: finish_decoded_dev)"""
+                               recipient_sk: bytes, checks: Optional[int], max_errors: int, correct: bool, repair: bool = False):
+    """reveal_sealed_checked (kind RevealCheck: finish_checked_dev's end, max_errors is not read), reveal_sealed_decoded
+    (RevealDecode: finish_decoded_dev's end) and, with repair, reveal_sealed_repaired (finish_erasures_dev's end around the rows the
+    sealed update refused; returns (output, report words, the results' status word) and leaves bit 16 of that word to the caller)"""
     from .device import DeviceBuffer
     a = aggregation
     sch, msch = a.committee_sharing_scheme, a.masking_scheme
@@ -1114,24 +1099,27 @@ def _reveal_sealed_with_checks(kind, name: str, aggregation: Aggregation, mask_j
     checks = reconstructor.default_checks(rows) if checks is None else checks
     unmasker = SecretUnmasker(msch)
     combiner = MaskCombiner(msch) if masks is not None else None
-    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the masked output, the
-    # combined mask and the output
+    # [0]: the mask job's status word, [1]: the clerking results', [2 .. 2 + words): the report, then the output and, with repair,
+    # the rows' ok words (two 32-bit words per entry)
     cap = max(n_out, 1)
     words = kind.HEAD + rows
-    d_buf = DeviceBuffer(2 + words + 3 * cap).zero()
-    d_masked, d_mask, d_out = (d_buf.at(2 + words + i * cap) for i in range(3))
+    first = 2 + words
+    d_buf = DeviceBuffer(first + cap + ((rows + 1) // 2 if repair else 0)).zero()
+    d_ok = d_buf.at(first + cap) if repair else 0
+    end = capi.CHECKED_END_ERASURES if repair else capi.CHECKED_END_LOCATE if kind is RevealCheck else capi.CHECKED_END_DECODE
     held = []
     if combiner is not None:
         held.append(combiner._feed_sealed_job(masks, combiner._sealed_job_dimension(n_out), recipient_pk, recipient_sk, d_buf.at(0)))
-        combiner.finish_dev(d_mask, n_out)
-    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks))
-    reconstructor._finish_with_checks(kind, d_masked, n_out, d_buf.at(2), max_errors, correct)
-    unmasker.unmask_dev(d_mask if combiner is not None else 0, d_masked, n_out, d_out)
+    held.append(reconstructor._feed_sealed_job(results, indices, row_len, recipient_pk, recipient_sk, d_buf.at(1), checks=checks, d_ok=d_ok))
+    unmasker.unmask_checked_jobs_dev(combiner, reconstructor, end, d_buf.at(first), n_out, d_buf.at(2), d_ok, max_errors, correct,
+                                     d_buf.at(0), d_buf.at(1), 16 if repair else 0)
     back = d_buf.to_numpy()
     del held
-    _raise_sealed_status(int(back[0]) | int(back[1]))
-    first = 2 + words + 2 * cap
-    return RecipientOutput(a.modulus, back[first:first + n_out].copy()), kind.from_words(back[2:2 + words].view(np.uint64).tolist())
+    status = int(back[1]) & 0xFFFFFFFF
+    _raise_sealed_status(int(back[0]) | (status & ~16 if repair else status))
+    output = RecipientOutput(a.modulus, back[first:first + n_out].copy())
+    report = back[2:first].view(np.uint64).tolist()
+    return (output, report, status) if repair else (output, kind.from_words(report))
 
 
 # ---- share-vector wire codec -------------------------------------------------------------

@@ -283,6 +283,21 @@ hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t*
                                         const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks, uint32_t n_rows,
                                         uint32_t max_errors, bool correct, size_t batches, size_t dimension, const ModParams& mod,
                                         const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
+// the UNMASKING form of one of the three finishes above (`end`), arguments and report as for that finish (d_ok and d_table are
+// read for Erasures only; max_errors is not read for Locate, is the cap 1 .. checks / 2 for Decode and 0 = up to 8 for Erasures):
+// where the finish stores a corrected secret v at d_out[e] this stores (canonical(v, mask_mod) - fold of the mask job's sum e under
+// mask_mod) mod mask_mod.  d_mask_lo / d_mask_hi: the mask job's `dimension` 128-bit sums - no entry at or beyond `dimension` is
+// read; nullptr: no mask, d_out[e] = v.  d_gate_masks / d_gate_results (nullptr: none): device words read when the kernel starts;
+// *d_gate_masks != 0 or (*d_gate_results & ~results_pass_bits) != 0 and nothing is stored to d_out - the report is written all
+// the same.  One launch (reveal_check_unmask_kernel, reveal_decode_unmask_kernel<false>), for Erasures the unchanged
+// reveal_erasure_setup_kernel + reveal_decode_unmask_kernel<true>; batches == 0 launches nothing
+enum class RevealUnmaskEnd { Locate, Decode, Erasures };
+hipError_t launch_reveal_unmask_finish(RevealUnmaskEnd end, const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr,
+                                       const uint64_t* d_xs, const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks,
+                                       uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches, size_t dimension,
+                                       const ModParams& mod, const MontParams& mont, const uint64_t* d_mask_lo, const int64_t* d_mask_hi,
+                                       const ModParams& mask_mod, const uint32_t* d_gate_masks, const uint32_t* d_gate_results,
+                                       uint32_t results_pass_bits, int64_t* d_out, uint64_t* d_report, hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

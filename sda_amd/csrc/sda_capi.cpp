@@ -2142,21 +2142,28 @@ extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstruct
 // positions d_ok marks (0 = erased, device words read by the kernels alone; NULL: none) and takes a job of one check too.  A refused
 // call leaves the job as it was.
 enum class CheckedEnd { Locate, Decode, Erasures };
-static int finish_with_checks(sda_secret_reconstructor* r, CheckedEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
-                              int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
-    const bool decode = end != CheckedEnd::Locate;
+// what every end of a checked job refuses, in this order (sda_secret_unmasker_unmask_checked_jobs_dev refuses the same)
+static int checked_end_refusals(const sda_secret_reconstructor* r, CheckedEnd end, unsigned max_errors, int policy, const int64_t* d_out,
+                                size_t out_cap, const uint64_t* d_report) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
     if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
     if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
     if (end == CheckedEnd::Decode && r->job_checks < 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
-    if (decode && max_errors > r->job_checks / 2)
+    if (end != CheckedEnd::Locate && max_errors > r->job_checks / 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
     if (!policy_known(policy)) return fail_policy(policy);
     if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
     if (out_cap < r->job_out) return fail(SDA_ERR_INVALID_ARGUMENT, "output buffer too small");
     if (!d_report) return fail(SDA_ERR_INVALID_ARGUMENT, "d_report is NULL");
+    return SDA_OK;
+}
+
+static int finish_with_checks(sda_secret_reconstructor* r, CheckedEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
+                              int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
+    const bool decode = end != CheckedEnd::Locate;
+    SDA_TRY(checked_end_refusals(r, end, max_errors, policy, d_out, out_cap, d_report));
     SDA_TRY(r->ctx.use());
     hipStream_t s = r->ctx.pick(stream);
     const size_t words = decode ? sda_reconstruct_decode_report_words(r->job_rows) : sda_reconstruct_report_words(r->job_rows);
@@ -2925,6 +2932,71 @@ extern "C" int sda_secret_unmasker_unmask_jobs_dev(sda_secret_unmasker_t* u, sda
         mc->core.begun = false;
     }
     r->job_begun = false;
+    return SDA_OK;
+}
+
+// The same last step for a CHECKED job: what finish_checked_dev / finish_decoded_dev / finish_erasures_dev (`end`) +
+// mask_combiner_finish_dev + unmask_dev give, report included, from the unmasking form of that finish's kernel - one launch, for
+// the erasure end the setup kernel before it; the two status words gate its stores.  The refusals, in the header's order, come
+// before the first launch and leave both jobs as they were
+extern "C" int sda_secret_unmasker_unmask_checked_jobs_dev(sda_secret_unmasker_t* u, sda_mask_combiner_t* mc, sda_secret_reconstructor_t* r,
+                                                           int end, const uint32_t* d_ok, unsigned max_errors, int policy,
+                                                           const uint32_t* d_status_masks, const uint32_t* d_status_results,
+                                                           uint32_t results_pass_bits, int64_t* d_out, size_t out_cap, uint64_t* d_report,
+                                                           void* stream) {
+    if (!u) return fail(SDA_ERR_INVALID_ARGUMENT, "unmasker is NULL");
+    if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
+    const MaskCore& uc = u->core;
+    const bool has_mask = uc.scheme.kind != SDA_MASKING_NONE;
+    if (!mc && has_mask) return fail(SDA_ERR_INVALID_ARGUMENT, "mask combiner is NULL: only a None unmasker goes without one");
+    if (mc) {
+        const sda_masking_scheme_t &a = uc.scheme, &b = mc->core.scheme;
+        if (a.kind != b.kind || (has_mask && a.modulus != b.modulus) || (a.kind == SDA_MASKING_CHACHA && a.dimension != b.dimension))
+            return fail(SDA_ERR_INVALID_ARGUMENT, "the unmasker and the mask combiner were built from different masking schemes");
+    }
+    if (has_mask && (uc.ctx.device != r->ctx.device || mc->core.ctx.device != r->ctx.device))
+        return fail(SDA_ERR_INVALID_ARGUMENT, "the unmasker lives on device %d, the mask combiner on device %d, the reconstructor on device %d",
+                    uc.ctx.device, mc->core.ctx.device, r->ctx.device);
+    if (!r->job_begun) return fail(SDA_ERR_STATE, "unmask before the reconstructor's begin");
+    if (end != SDA_CHECKED_END_LOCATE && end != SDA_CHECKED_END_DECODE && end != SDA_CHECKED_END_ERASURES)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "end = %d: SDA_CHECKED_END_LOCATE, SDA_CHECKED_END_DECODE or SDA_CHECKED_END_ERASURES", end);
+    const CheckedEnd which = end == SDA_CHECKED_END_LOCATE ? CheckedEnd::Locate : end == SDA_CHECKED_END_DECODE ? CheckedEnd::Decode : CheckedEnd::Erasures;
+    SDA_TRY(checked_end_refusals(r, which, max_errors, policy, d_out, out_cap, d_report));
+    if (has_mask && !mc->core.begun) return fail(SDA_ERR_STATE, "unmask before the mask combiner's begin");
+    if (uc.rust_signed || r->job_acc.rust_signed || (has_mask && mc->core.acc.rust_signed))
+        return fail(SDA_ERR_UNSUPPORTED, "unmask_checked_jobs_dev reads 128-bit sums: SDA_VALUES_RUST_SIGNED takes the finish + finish_dev + unmask_dev");
+    const size_t len = r->job_out;
+    if (has_mask && mc->core.job_dimension != len)                            // full.rs:58, chacha.rs:83
+        return fail(SDA_ERR_ASSERTION, "assertion failed: `(left == right)` (mask %zu, masked secrets %zu)", mc->core.job_dimension, len);
+    if (results_pass_bits != 0 && results_pass_bits != 16)
+        return fail(SDA_ERR_INVALID_ARGUMENT, "results_pass_bits = %u: 0, or 16 for the caller who repairs refused boxes", results_pass_bits);
+    SDA_TRY(r->ctx.use());
+    hipStream_t s = r->ctx.pick(stream);
+    const bool decode = which != CheckedEnd::Locate;
+    const size_t words = decode ? sda_reconstruct_decode_report_words(r->job_rows) : sda_reconstruct_report_words(r->job_rows);
+    if (len && which == CheckedEnd::Erasures) SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
+    HIP_TRY(hipMemsetAsync(d_report, 0, words * 8, s));
+    HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, decode ? 16 : 8, s));         // as finish_with_checks initialises it
+    if (len) {
+        const AccState* m = has_mask ? &mc->core.acc : nullptr;
+        const RevealUnmaskEnd kernel = which == CheckedEnd::Locate ? RevealUnmaskEnd::Locate : which == CheckedEnd::Decode ? RevealUnmaskEnd::Decode : RevealUnmaskEnd::Erasures;
+        const uint32_t cap = which == CheckedEnd::Decode && !max_errors ? r->job_checks / 2 : max_errors;
+        HIP_TRY(launch_reveal_unmask_finish(kernel, r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
+                                            r->d_xs.as<uint64_t>(), d_ok, which == CheckedEnd::Erasures ? r->d_erase.as<uint64_t>() : nullptr,
+                                            r->k, r->job_checks, (uint32_t)r->job_rows, cap, policy == SDA_CHECK_CORRECT,
+                                            (r->dimension + r->k - 1) / r->k, r->dimension, r->mod, r->mont, m ? m->lo.as<uint64_t>() : nullptr,
+                                            m ? m->hi.as<int64_t>() : nullptr, has_mask ? mc->core.mod : r->mod, d_status_masks,
+                                            d_status_results, results_pass_bits, d_out, d_report, s));
+        NOTE_CALL_KERNELS("%s", which == CheckedEnd::Erasures ? "reveal_erasure_setup_kernel + reveal_decode_unmask_kernel<true>"
+                                : decode                      ? "reveal_decode_unmask_kernel<false>"
+                                                              : "reveal_check_unmask_kernel");
+    }
+    if (mc) {                                                                 // as sda_mask_combiner_finish_dev ends its job
+        if (has_mask && mc->core.d_seeds.p) HIP_TRY(hipMemsetAsync(mc->core.d_seeds.p, 0, mc->core.d_seeds.cap, s));
+        mc->core.begun = false;
+    }
+    r->job_begun = false;
+    r->job_checks = 0;
     return SDA_OK;
 }
 

@@ -1724,6 +1724,319 @@ __global__ __launch_bounds__(kThreads) void reveal_erasure_finish_kernel(RevealE
     }
 }
 
+// The UNMASKING forms of the three finishes (sda_secret_unmasker_unmask_checked_jobs_dev): the same lane = batch, the same
+// verdicts and the same report, and where the finishes store a corrected secret v these store (canonical(v, q_mask) - fold of the
+// mask job's sum, q_mask) mod q_mask, as unmask_finish_kernel does for a plain job - the masked output and the combined mask
+// never reach memory.  They stand BESIDE the three kernels above, whose text and code they leave alone: those are measured
+// products.  The locating form is its own kernel; the decoding and the erasure form are the two instances of one template, the
+// erasure steps under `if constexpr`.
+struct RevealUnmask {
+    const uint64_t* m_lo;        // [dimension]: the mask job's sums - NOT batches * k; nullptr: no mask, the store is v (none.rs:28-33)
+    const int64_t* m_hi;
+    ModParams m_mod;
+    const uint32_t* gate_a;      // the status word of the masks' sealed update (nullptr: none): non-zero = nothing is stored
+    const uint32_t* gate_b;      // the one of the clerking results': a bit outside pass_b = nothing is stored
+    uint32_t pass_b;
+};
+
+// read once when the kernel starts; wave-uniform.  A shut gate suppresses the stores to `out` and nothing else
+static __device__ __forceinline__ bool unmask_gate_shut(const RevealUnmask& U) {
+    return (U.gate_a && *U.gate_a != 0) || (U.gate_b && (*U.gate_b & ~U.pass_b) != 0);
+}
+
+// fold_group for the mask sums: element j is loaded only when j < have, the elements of the batch below `dimension`
+template <int N>
+static __device__ __forceinline__ void fold_group_guarded(const uint64_t* __restrict__ lo, const int64_t* __restrict__ hi, uint32_t have,
+                                                          const ModParams& mod, uint64_t (&o)[4]) {
+    FoldState f[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        uint64_t l = 0;
+        int64_t h = 0;
+        if ((uint32_t)j < have) { l = lo[j]; h = hi[j]; }
+        f[j] = fold_head(l, h, mod);
+    }
+    for (int bit = 63; bit >= 0; --bit) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) fold_step(f[j], bit, mod.m);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] = fold_tail(f[j], mod.m);
+}
+
+// v[0 .. n): the corrected secrets of elements e0 .. e0 + n of one batch, `have` of them below `dimension` (0 for a lane that is
+// not live); n is wave-uniform.  Unmasks and stores those; the padding is neither read from the mask job nor stored (batched.rs:94)
+static __device__ __forceinline__ void unmask_store_group(const RevealUnmask& U, bool shut, uint32_t n, uint64_t e0, uint32_t have,
+                                                          uint64_t (&v)[4], int64_t* __restrict__ out) {
+    if (U.m_lo != nullptr) {                               // wave-uniform
+        const uint64_t at = have ? e0 : 0;
+        uint64_t mk[4] = {0, 0, 0, 0};
+        if (n >= 4) fold_group_guarded<4>(U.m_lo + at, U.m_hi + at, have, U.m_mod, mk);
+        else if (n == 3) fold_group_guarded<3>(U.m_lo + at, U.m_hi + at, have, U.m_mod, mk);
+        else if (n == 2) fold_group_guarded<2>(U.m_lo + at, U.m_hi + at, have, U.m_mod, mk);
+        else fold_group_guarded<1>(U.m_lo + at, U.m_hi + at, have, U.m_mod, mk);
+        // the reference subtracts under the masking scheme's modulus whatever the sharing modulus is (full.rs:60-63,
+        // chacha.rs:86-89): a masked value may be >= q_mask
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = submod(canon_i64((int64_t)v[j], U.m_mod.m, U.m_mod.mu), mk[j], U.m_mod.m);
+    }
+    if (shut) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if ((uint32_t)j < have) out[e0 + j] = (int64_t)v[j];
+}
+
+// the elements of group s0 .. s0 + n of batch b that lie below `dimension`
+static __device__ __forceinline__ uint32_t unmask_group_have(bool live, uint64_t e0, uint32_t n, uint64_t dimension) {
+    if (!live || e0 >= dimension) return 0;
+    return dimension - e0 < n ? (uint32_t)(dimension - e0) : n;
+}
+
+__global__ __launch_bounds__(kThreads) void reveal_check_unmask_kernel(RevealCheckJob J, RevealUnmask U, int64_t* __restrict__ out,
+                                                                       unsigned long long* __restrict__ report) {
+    __shared__ unsigned int wg_count[3];                   // bad, located, corrected batches of this workgroup
+    __shared__ unsigned long long wg_first;
+    if (threadIdx.x == 0) {
+        wg_count[0] = wg_count[1] = wg_count[2] = 0;
+        wg_first = ~0ull;
+    }
+    __syncthreads();
+    const bool shut = unmask_gate_shut(U);
+    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = b < J.batches;
+    const int lane = threadIdx.x & 63;
+    const uint32_t width = J.k + J.checks;
+    const uint64_t* lo = J.lo + (live ? b : 0) * width;
+    const int64_t* hi = J.hi + (live ? b : 0) * width;
+    const uint64_t m = J.mod.m;
+
+    uint64_t S[kMaxChecks];
+#pragma unroll
+    for (int g = 0; g < kMaxChecks / 4; ++g) {
+        uint64_t o[4] = {0, 0, 0, 0};
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
+    }
+    uint64_t any = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
+    const bool bad = live && any != 0;
+
+    uint32_t where = 0, fits = 0;
+    if (bad && J.checks >= 2 && S[0] != 0) {
+        for (uint32_t i = 0; i < J.n_rows; ++i) {
+            const uint64_t x = J.xs[i];
+            bool fit = true;
+#pragma unroll
+            for (int d = 0; d + 1 < kMaxChecks; ++d)
+                if ((uint32_t)(d + 1) < J.checks) fit = fit && mont_redc(mul64x64(x, S[d]), m, J.pinv) == S[d + 1];
+            if (fit) { where = i; ++fits; }
+        }
+    }
+    const bool located = fits == 1;
+    const bool fix = located && J.correct != 0;
+
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
+        const uint64_t e0 = b * J.k + s0;
+        const uint32_t have = unmask_group_have(live, e0, n, J.dimension);
+        if (fix) {                                         // under the sharing modulus, before the canonicalisation under q_mask
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((uint32_t)j < have)
+                    o[j] = submod(o[j], mont_redc(mul64x64(J.corr[(uint64_t)(s0 + j) * J.n_rows + where], S[0]), m, J.pinv), m);
+        }
+        unmask_store_group(U, shut, n, e0, have, o, out);
+    }
+
+    // ---- the report: reveal_check_finish_kernel's, whatever the gate says ----
+    const unsigned long long bad_lanes = __ballot(bad), located_lanes = __ballot(located), fixed_lanes = __ballot(fix);
+    if (lane == 0 && bad_lanes != 0) {
+        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
+        if (located_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(located_lanes));
+        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
+        atomicMin(&wg_first, (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+    }
+    unsigned long long pending = located_lanes;
+    while (pending) {                                      // one atomic per distinct blamed position of the wave
+        const int leader = __ffsll((long long)pending) - 1;
+        const uint32_t pos = (uint32_t)__shfl((int)where, leader);
+        const unsigned long long same = __ballot(located && where == pos);
+        if (lane == leader) atomicAdd(&report[4 + pos], (unsigned long long)__popcll(same));
+        pending &= ~same;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
+        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
+        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
+        atomicMin(&report[3], wg_first);
+    }
+}
+
+// kErasures false: reveal_decode_finish_kernel's verdicts (J.table is not read, J.cap is the caller's cap); true:
+// reveal_erasure_finish_kernel's around the table's erased positions
+template <bool kErasures>
+__global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealErasureJob J, RevealUnmask U, int64_t* __restrict__ out,
+                                                                        unsigned long long* __restrict__ report) {
+    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
+    __shared__ unsigned int wg_most;                       // the largest nu
+    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
+    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
+    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
+    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        wg_most = 0;
+        wg_first[0] = wg_first[1] = ~0ull;
+    }
+    __syncthreads();
+    const bool shut = unmask_gate_shut(U);
+    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool live = b < J.batches;
+    const int lane = threadIdx.x & 63;
+    const uint32_t width = J.k + J.checks;
+    const uint64_t* lo = J.lo + (live ? b : 0) * width;
+    const int64_t* hi = J.hi + (live ? b : 0) * width;
+    const uint64_t m = J.mod.m;
+    bool over = false;
+    uint32_t f = 0;                                        // the erased positions, <= checks
+    if constexpr (kErasures) {
+        over = J.table[kEraseOver] != 0;
+        f = over ? 0 : (uint32_t)J.table[kEraseCount];
+    }
+    const uint32_t len = J.checks - f;                     // the (modified) syndromes that are decoded
+    const uint32_t cap = kErasures ? (J.cap < len / 2 ? J.cap : len / 2) : J.cap;
+
+    uint64_t S[kMaxChecks], T[kMaxChecks];                 // kErasures false: T is S
+#pragma unroll
+    for (int g = 0; g < kMaxChecks / 4; ++g) {
+        uint64_t o[4] = {0, 0, 0, 0};
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) S[4 * g + j] = T[4 * g + j] = o[j];        // 0 from J.checks on
+    }
+    if constexpr (kErasures) {
+#pragma unroll 1
+        for (uint32_t q = 0; q < f; ++q) erase_fold_point(T, J.checks, J.xs[J.table[kErasePos + q]], m, J.pinv);
+        erase_keep(T, len);
+    }
+    uint64_t any = 0, any_s = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxChecks; ++d) {
+        any |= T[d];
+        any_s |= S[d];
+    }
+    const bool bad = live && !over && any != 0;
+
+    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
+    if (bad && cap >= 1) {
+        uint64_t C[kDecodeErrors + 1];
+        const uint32_t L = decode_bm(T, len, m, J.pinv, C);
+        bool rooted = false;
+        if (L >= 1 && L <= cap) {
+            if constexpr (kErasures)
+                rooted = decode_roots_live(C, cap, J.n_rows, J.xs, J.table + kEraseInv, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L;
+            else
+                rooted = decode_roots(C, cap, J.n_rows, J.xs, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L;
+        }
+        if (rooted) {
+            uint64_t Om[kDecodeErrors];
+            decode_omega(T, C, cap, m, J.pinv, Om);
+            for (uint32_t j = 0; j < L; ++j) {
+                const uint32_t at = dec_pos[j][threadIdx.x];
+                uint64_t Y = decode_magnitude(C, Om, L, J.xs[at], m, J.pinv);
+                if constexpr (kErasures) Y = dec_mm(Y, J.table[kEraseInv + at], m, J.pinv);
+                dec_y[j][threadIdx.x] = Y;
+            }
+            nu = L;
+        }
+    }
+    const bool decoded = nu != 0;
+    const bool fix = decoded && J.correct != 0;
+    // the erased positions' share: a consistent or decoded batch whose sums are not all zero
+    const bool mend = kErasures && live && f != 0 && J.correct != 0 && any_s != 0 && (!bad || decoded);
+    uint64_t Ye[kEraseMax];
+    if constexpr (kErasures) {
+#pragma unroll
+        for (int j = 0; j < kEraseMax; ++j) Ye[j] = 0;
+        if (mend) {
+            for (uint32_t q = 0; q < nu; ++q) erase_remove(S, f, dec_y[q][threadIdx.x], J.xs[dec_pos[q][threadIdx.x]], m, J.pinv);
+            erase_magnitudes(S, f, J.table + kEraseRows, m, J.pinv, Ye);
+        }
+    }
+
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
+        const uint64_t e0 = b * J.k + s0;
+        const uint32_t have = unmask_group_have(live, e0, n, J.dimension);
+        if (fix || mend) {                                 // under the sharing modulus, before the canonicalisation under q_mask
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if ((uint32_t)j >= have) continue;
+                uint64_t v = o[j];
+                const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
+                if (fix) {
+                    for (uint32_t q = 0; q < nu; ++q)
+                        v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
+                }
+                if constexpr (kErasures) {
+                    if (mend) v = erase_apply(v, corr, J.table, f, Ye, m, J.pinv);
+                }
+                o[j] = v;
+            }
+        }
+        unmask_store_group(U, shut, n, e0, have, o, out);
+    }
+
+    // ---- the report: the two finishes', whatever the gate says ----
+    const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
+    const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
+    if (lane == 0 && bad_lanes != 0) {
+        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
+        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
+        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
+        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
+    }
+    if (decoded_lanes != 0) {                              // wave-uniform
+        for (uint32_t j = 0; j < cap; ++j) {
+            const unsigned long long with = __ballot(nu == j + 1);
+            if (lane == 0 && with != 0) {
+                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
+                atomicMax(&wg_most, j + 1);
+            }
+            const bool has = j < nu;
+            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
+            unsigned long long pending = __ballot(has);
+            while (pending) {                              // one atomic per distinct position the wave blames in slot j
+                const int leader = __ffsll((long long)pending) - 1;
+                const uint32_t pos = (uint32_t)__shfl((int)mine, leader);
+                const unsigned long long same = __ballot(has && mine == pos);
+                if (lane == leader) atomicAdd(&report[16 + pos], (unsigned long long)__popcll(same));
+                pending &= ~same;
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
+        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
+        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
+        atomicMin(&report[3], wg_first[0]);
+        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
+        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
+        for (int j = 0; j < kDecodeErrors; ++j)
+            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
+    }
+}
+
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
 // =================================================================================================
@@ -2773,6 +3086,41 @@ hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t*
     const RevealErasureJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, d_table, k, checks, n_rows, correct ? 1u : 0u,
                              max_errors ? max_errors : (uint32_t)kDecodeErrors, batches, dimension, mod, mont.pinv};
     reveal_erasure_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
+    return hipGetLastError();
+}
+
+hipError_t launch_reveal_unmask_finish(RevealUnmaskEnd end, const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr,
+                                       const uint64_t* d_xs, const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks,
+                                       uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches, size_t dimension,
+                                       const ModParams& mod, const MontParams& mont, const uint64_t* d_mask_lo, const int64_t* d_mask_hi,
+                                       const ModParams& mask_mod, const uint32_t* d_gate_masks, const uint32_t* d_gate_results,
+                                       uint32_t results_pass_bits, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
+    if (batches == 0) return hipSuccess;
+    if (checks == 0 || checks > (uint32_t)kMaxChecks || n_rows == 0 || n_rows > 65535) return hipErrorInvalidValue;   // dec_pos is 16 bits wide
+    if (end != RevealUnmaskEnd::Locate && max_errors > checks / 2) return hipErrorInvalidValue;
+    if (end == RevealUnmaskEnd::Decode && (checks < 2 || max_errors == 0)) return hipErrorInvalidValue;
+    if (end == RevealUnmaskEnd::Erasures && d_table == nullptr) return hipErrorInvalidValue;
+    const uint64_t blocks = ceil_div(batches, kThreads);
+    if (hipError_t e = grid_check(blocks)) return e;
+    const uint32_t fix = correct ? 1u : 0u;
+    const RevealUnmask U{d_mask_lo, d_mask_hi, d_mask_lo ? mask_mod : mod, d_gate_masks, d_gate_results, results_pass_bits};
+    unsigned long long* report = reinterpret_cast<unsigned long long*>(d_report);
+    if (end == RevealUnmaskEnd::Locate) {
+        const RevealCheckJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, fix, batches, dimension, mod, mont.pinv};
+        reveal_check_unmask_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
+        return hipGetLastError();
+    }
+    RevealErasureJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, nullptr, k, checks, n_rows, fix, max_errors, batches, dimension, mod, mont.pinv};
+    if (end == RevealUnmaskEnd::Decode) {
+        reveal_decode_unmask_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
+        return hipGetLastError();
+    }
+    reveal_erasure_setup_kernel<<<dim3(1), dim3(kThreads), 0, s>>>(d_ok, d_xs, n_rows, checks, mont.p, mont.pinv, h_to_mont(1, mont.p), d_table,
+                                                                   report);
+    if (hipError_t e = hipGetLastError()) return e;
+    J.table = d_table;
+    if (max_errors == 0) J.cap = (uint32_t)kDecodeErrors;
+    reveal_decode_unmask_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
     return hipGetLastError();
 }
 

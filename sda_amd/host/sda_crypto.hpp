@@ -584,6 +584,21 @@ struct SecretUnmasker {
                                                  values.second.size(), out.data()));
         return out;
     }
+    // the recipient's last step for a CHECKED reconstructor job (begin_checked_dev, every position fed) and a mask combiner job,
+    // through ONE call (sda_secret_unmasker_unmask_checked_jobs_dev): end = SDA_CHECKED_END_LOCATE / _DECODE / _ERASURES names the
+    // finish whose verdicts and report (d_report, that finish's words) are wanted; d_out is that finish's output unmasked, with
+    // neither the masked output nor the combined mask in device memory.  Ends both jobs.  d_status_*: the status words of the jobs'
+    // sealed updates as gates - *d_status_masks != 0 or (*d_status_results & ~results_pass_bits) != 0 when the kernel runs and
+    // nothing is stored to d_out (the report is written all the same); results_pass_bits: 0, or 16 for the caller who repairs
+    // refused boxes.  combiner: null for a None unmasker only.  Nothing synchronises or reaches the host
+    void unmask_checked_jobs_dev(MaskCombiner* combiner, SecretReconstructor& reconstructor, int end, int64_t* d_out, size_t out_cap,
+                                 uint64_t* d_report, const uint32_t* d_ok = nullptr, unsigned max_errors = 0, bool correct = false,
+                                 const uint32_t* d_status_masks = nullptr, const uint32_t* d_status_results = nullptr,
+                                 uint32_t results_pass_bits = 0, void* stream = nullptr) {
+        detail::check(sda_secret_unmasker_unmask_checked_jobs_dev(h, combiner ? combiner->h : nullptr, reconstructor.h, end, d_ok, max_errors,
+                                                                  correct ? SDA_CHECK_CORRECT : SDA_CHECK_REPORT, d_status_masks,
+                                                                  d_status_results, results_pass_bits, d_out, out_cap, d_report, stream));
+    }
 };
 
 /// The recipient's last step (receive.rs:148-156) for a MaskCombiner job and a SecretReconstructor job, both begun and fed on the
