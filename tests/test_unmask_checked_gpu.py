@@ -3,7 +3,8 @@ combiner job in one call.  Every case of tests/unmask_checked_cases.py is bit-ex
 report, in sentinel-filled buffers - and against the three-call chain (finish_checked_dev / finish_decoded_dev / finish_erasures_dev,
 sda_mask_combiner_finish_dev, sda_secret_unmasker_unmask_dev) run on twin jobs; then the shut gate, the refusal order with several
 faults per call, the handles reused across ends, a stream of the caller's, dimension 0 and the loop on sealed bytes through the
-three reveal_sealed_* functions.  tests/test_unmask_checked_reach.py proves on the CPU what the table contains."""
+three reveal_sealed_* functions.  tests/test_unmask_checked_reach.py proves on the CPU what the table contains.  The table's borrowed
+cases feed the rows of the finish tables' wide and steered cases, in one plaintext update_dev call."""
 import numpy as np
 import pytest
 
@@ -45,7 +46,8 @@ class Handles:
         from sda_amd.device import DeviceBuffer, DeviceBytes
         case = case or self.case
         b = kc.build(case.name)
-        pos, B = len(case.indices), kc.batches(case)
+        pos, B = len(case.indices), b.rows.shape[1]                                          # a borrowed case's rows are its source's, whole
+        assert B >= kc.batches(case)
         if checked:
             self.reconstructor.begin_checked_dev(case.indices, pos, B, case.checks, stream)
         else:
