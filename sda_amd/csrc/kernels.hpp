@@ -255,49 +255,56 @@ hipError_t launch_addsub_mod(const int64_t* d_a, const int64_t* d_b, size_t len,
 hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_recon_hi, const ModParams& recon_mod,
                                 const uint64_t* d_mask_lo, const int64_t* d_mask_hi, const ModParams& mask_mod, size_t len,
                                 const uint32_t* d_gate_a, const uint32_t* d_gate_b, int64_t* d_out, hipStream_t s);
-// the finish of a checked reconstruction job: accumulators [batches][k + checks] (k secrets, then `checks` syndromes, 1 .. 16),
-// d_corr [k][n_rows] = R[s][i] / u_i and d_xs [n_rows] = the evaluation points, both in Montgomery form.  Per batch: fold, test
-// the syndromes, locate (exactly one position i with S_{d+1} = x_i S_d for every d < checks - 1; checks == 1 locates nothing),
-// under `correct` subtract corr[s][i] S_0, store d_out[b k + s] for b k + s < dimension.  d_report [4 + n_rows], initialised by
-// the caller to {0, 0, 0, 2^64 - 1, 0 ...}: bad, located, corrected batches, first bad batch, batches that blame position i
-hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                      uint32_t k, uint32_t checks, uint32_t n_rows, bool correct, size_t batches, size_t dimension,
-                                      const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
-// the DECODING finish of the same job: per batch with a non-zero syndrome, Berlekamp-Massey + root search + magnitudes
-// (reveal_decode.hpp); decoded with nu <= max_errors <= checks / 2 positions = all `checks` syndromes are reproduced by nu positions
-// of the job.  Under `correct` the secrets lose sum_j corr[s][i_j] Y_j.  d_report [16 + n_rows], initialised by the caller to 0
-// with [3] = [4] = 2^64 - 1: bad, decoded, corrected batches, first bad, first undecoded batch, largest nu, 0, 0, batches decoded
-// with nu = 1 .. 8, batches that blame position i
-hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                       uint32_t k, uint32_t checks, uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches,
-                                       size_t dimension, const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report,
-                                       hipStream_t s);
-// the ERASURE finish of the same job: d_ok [n_rows] device words, 0 = position i is erased whatever it added (nullptr: none);
-// d_table: reveal_erasure_table_words(n_rows) device words of scratch.  reveal_erasure_setup_kernel (one workgroup) compacts the
-// f erased positions and builds the per-job tables, reveal_erasure_finish_kernel decodes the modified syndromes T_j = sum_m
-// gamma_m S_{j+m}, j < checks - f, with at most min(max_errors or 8, (checks - f) / 2) non-erased positions and, under `correct`,
-// solves the erased magnitudes and subtracts the correction over both sets.  d_report as for the decoding finish, with [6] = f and
-// [7] = 1 when f > checks (then d_out is the plain fold and nothing else is reported).  checks 1 .. 16, max_errors <= checks / 2
+// the finish of a checked reconstruction job, one of three ends: accumulators [batches][k + checks] (k secrets, then `checks`
+// syndromes, 1 .. 16), d_corr [k][n_rows] = R[s][i] / u_i and d_xs [n_rows] = the evaluation points, both in Montgomery form,
+// n_rows 1 .. 65535.  Per batch: fold, test the syndromes, judge, correct under `correct`, store d_out[b k + s] for b k + s < dimension
+//   Locate - exactly one position i with S_{d+1} = x_i S_d for every d < checks - 1 (checks == 1 locates nothing); under `correct`
+// subtract corr[s][i] S_0.  d_report [4 + n_rows], initialised by the caller to {0, 0, 0, 2^64 - 1, 0 ...}: bad, located,
+// corrected batches, first bad batch, batches that blame position i
+//   Decode - per batch with a non-zero syndrome, Berlekamp-Massey + root search + magnitudes (reveal_decode.hpp); decoded with
+// nu <= max_errors <= checks / 2 positions = all `checks` syndromes are reproduced by nu positions of the job.  Under `correct` the
+// secrets lose sum_j corr[s][i_j] Y_j.  d_report [16 + n_rows], initialised by the caller to 0 with [3] = [4] = 2^64 - 1: bad,
+// decoded, corrected batches, first bad, first undecoded batch, largest nu, 0, 0, batches decoded with nu = 1 .. 8, batches that
+// blame position i.  checks 2 .. 16, max_errors 1 .. checks / 2
+//   Erasures - d_ok [n_rows] device words, 0 = position i is erased whatever it added (nullptr: none); d_table:
+// reveal_erasure_table_words(n_rows) device words of scratch.  reveal_erasure_setup_kernel (one workgroup) compacts the f erased
+// positions and builds the per-job tables, the finish decodes the modified syndromes T_j = sum_m gamma_m S_{j+m}, j < checks - f,
+// with at most min(max_errors or 8, (checks - f) / 2) non-erased positions and, under `correct`, solves the erased magnitudes and
+// subtracts the correction over both sets.  d_report as for Decode, with [6] = f and [7] = 1 when f > checks (then d_out is the
+// plain fold and nothing else is reported).  checks 1 .. 16, max_errors <= checks / 2
+enum class RevealEnd { Locate, Decode, Erasures };
+struct RevealFinishJob {
+    const uint64_t* d_acc_lo;
+    const int64_t* d_acc_hi;
+    const uint64_t* d_corr;
+    const uint64_t* d_xs;
+    const uint32_t* d_ok;        // Erasures only
+    uint64_t* d_table;           // Erasures only
+    uint32_t k, checks, n_rows, max_errors;   // max_errors: not read for Locate
+    bool correct;
+    size_t batches, dimension;
+    ModParams mod;
+    MontParams mont;
+};
+// the unmasking form of a finish: where the finish stores a corrected secret v at d_out[e] it stores (canonical(v, mask_mod) -
+// fold of the mask job's sum e under mask_mod) mod mask_mod.  d_mask_lo / d_mask_hi: the mask job's `dimension` 128-bit sums - no
+// entry at or beyond `dimension` is read; nullptr: no mask, d_out[e] = v.  d_gate_masks / d_gate_results (nullptr: none): device
+// words read when the kernel starts; *d_gate_masks != 0 or (*d_gate_results & ~results_pass_bits) != 0 and nothing is stored to
+// d_out - the report is written all the same
+struct RevealFinishUnmask {
+    const uint64_t* d_mask_lo;
+    const int64_t* d_mask_hi;
+    ModParams mask_mod;
+    const uint32_t* d_gate_masks;
+    const uint32_t* d_gate_results;
+    uint32_t results_pass_bits;
+};
 size_t reveal_erasure_table_words(size_t n_rows);
-hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                        const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks, uint32_t n_rows,
-                                        uint32_t max_errors, bool correct, size_t batches, size_t dimension, const ModParams& mod,
-                                        const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s);
-// the UNMASKING form of one of the three finishes above (`end`), arguments and report as for that finish (d_ok and d_table are
-// read for Erasures only; max_errors is not read for Locate, is the cap 1 .. checks / 2 for Decode and 0 = up to 8 for Erasures):
-// where the finish stores a corrected secret v at d_out[e] this stores (canonical(v, mask_mod) - fold of the mask job's sum e under
-// mask_mod) mod mask_mod.  d_mask_lo / d_mask_hi: the mask job's `dimension` 128-bit sums - no entry at or beyond `dimension` is
-// read; nullptr: no mask, d_out[e] = v.  d_gate_masks / d_gate_results (nullptr: none): device words read when the kernel starts;
-// *d_gate_masks != 0 or (*d_gate_results & ~results_pass_bits) != 0 and nothing is stored to d_out - the report is written all
-// the same.  One launch (reveal_check_unmask_kernel, reveal_decode_unmask_kernel<false>), for Erasures the unchanged
-// reveal_erasure_setup_kernel + reveal_decode_unmask_kernel<true>; batches == 0 launches nothing
-enum class RevealUnmaskEnd { Locate, Decode, Erasures };
-hipError_t launch_reveal_unmask_finish(RevealUnmaskEnd end, const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr,
-                                       const uint64_t* d_xs, const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks,
-                                       uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches, size_t dimension,
-                                       const ModParams& mod, const MontParams& mont, const uint64_t* d_mask_lo, const int64_t* d_mask_hi,
-                                       const ModParams& mask_mod, const uint32_t* d_gate_masks, const uint32_t* d_gate_results,
-                                       uint32_t results_pass_bits, int64_t* d_out, uint64_t* d_report, hipStream_t s);
+// one launch - reveal_{check,decode,erasure}_finish_kernel, with `unmask` reveal_check_unmask_kernel or
+// reveal_decode_unmask_kernel<false | true> - for Erasures reveal_erasure_setup_kernel before it.  batches == 0 launches nothing
+// but, for Erasures, the setup kernel (it writes the report's [6] and [7])
+hipError_t launch_reveal_finish(RevealEnd end, const RevealFinishJob& job, const RevealFinishUnmask* unmask, int64_t* d_out,
+                                uint64_t* d_report, hipStream_t s);
 // full.rs:21-35 with the on-device CSPRNG, `participants` vectors at once: mask[p][i] uniform (DRBG stream
 // first_stream + p), masked[p][i] = (s[p][i] + mask[p][i]) mod m
 hipError_t launch_full_mask_drbg(const int64_t* d_secrets, size_t secrets_stride, size_t participants, size_t len,

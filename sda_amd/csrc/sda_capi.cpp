@@ -2141,17 +2141,16 @@ extern "C" int sda_secret_reconstructor_begin_checked_dev(sda_secret_reconstruct
 // decoding one with max_errors, 0 = checks / 2 (report [16 + rows], two such words), or the erasure one, which decodes around the
 // positions d_ok marks (0 = erased, device words read by the kernels alone; NULL: none) and takes a job of one check too.  A refused
 // call leaves the job as it was.
-enum class CheckedEnd { Locate, Decode, Erasures };
 // what every end of a checked job refuses, in this order (sda_secret_unmasker_unmask_checked_jobs_dev refuses the same)
-static int checked_end_refusals(const sda_secret_reconstructor* r, CheckedEnd end, unsigned max_errors, int policy, const int64_t* d_out,
+static int checked_end_refusals(const sda_secret_reconstructor* r, RevealEnd end, unsigned max_errors, int policy, const int64_t* d_out,
                                 size_t out_cap, const uint64_t* d_report) {
     if (!r) return fail(SDA_ERR_INVALID_ARGUMENT, "reconstructor is NULL");
     if (!r->job_begun) return fail(SDA_ERR_STATE, "finish before begin");
     if (!r->job_checks) return fail(SDA_ERR_STATE, "the job was begun with begin_dev: it carries no checks, finish_dev ends it");
     if (r->job_fed != r->job_rows) return fail(SDA_ERR_STATE, "%zu of the job's %zu positions were not fed", r->job_rows - r->job_fed, r->job_rows);
-    if (end == CheckedEnd::Decode && r->job_checks < 2)
+    if (end == RevealEnd::Decode && r->job_checks < 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "a job with one check decodes nothing: finish_checked_dev ends it");
-    if (end != CheckedEnd::Locate && max_errors > r->job_checks / 2)
+    if (end != RevealEnd::Locate && max_errors > r->job_checks / 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "max_errors = %u: %u checks decode at most %u positions per batch", max_errors, r->job_checks, r->job_checks / 2);
     if (!policy_known(policy)) return fail_policy(policy);
     if (r->job_out > 0 && !d_out) return fail(SDA_ERR_INVALID_ARGUMENT, "d_out is NULL");
@@ -2160,34 +2159,34 @@ static int checked_end_refusals(const sda_secret_reconstructor* r, CheckedEnd en
     return SDA_OK;
 }
 
-static int finish_with_checks(sda_secret_reconstructor* r, CheckedEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
+// the launch of an end, plain (unmask == nullptr) or unmasking, on a job and a report the caller has prepared.  max_errors == 0:
+// the Decode end's cap is checks / 2, stated here; the Erasures end's is the launcher's
+static int launch_checked_end(sda_secret_reconstructor* r, RevealEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
+                              const RevealFinishUnmask* unmask, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
+    static const char* const kernels[2][3] = {
+        {"reveal_check_finish_kernel", "reveal_decode_finish_kernel", "reveal_erasure_setup_kernel + reveal_erasure_finish_kernel"},
+        {"reveal_check_unmask_kernel", "reveal_decode_unmask_kernel<false>", "reveal_erasure_setup_kernel + reveal_decode_unmask_kernel<true>"}};
+    const bool erasures = end == RevealEnd::Erasures;
+    const RevealFinishJob job{r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(), r->d_xs.as<uint64_t>(),
+                              erasures ? d_ok : nullptr, erasures ? r->d_erase.as<uint64_t>() : nullptr, r->k, r->job_checks,
+                              (uint32_t)r->job_rows, end == RevealEnd::Decode && !max_errors ? r->job_checks / 2 : max_errors,
+                              policy == SDA_CHECK_CORRECT, (r->dimension + r->k - 1) / r->k, r->dimension, r->mod, r->mont};
+    HIP_TRY(launch_reveal_finish(end, job, unmask, d_out, d_report, s));
+    NOTE_CALL_KERNELS("%s", kernels[unmask ? 1 : 0][(int)end]);
+    return SDA_OK;
+}
+
+static int finish_with_checks(sda_secret_reconstructor* r, RevealEnd end, const uint32_t* d_ok, unsigned max_errors, int policy,
                               int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
-    const bool decode = end != CheckedEnd::Locate;
+    const bool decode = end != RevealEnd::Locate;
     SDA_TRY(checked_end_refusals(r, end, max_errors, policy, d_out, out_cap, d_report));
     SDA_TRY(r->ctx.use());
     hipStream_t s = r->ctx.pick(stream);
     const size_t words = decode ? sda_reconstruct_decode_report_words(r->job_rows) : sda_reconstruct_report_words(r->job_rows);
     HIP_TRY(hipMemsetAsync(d_report, 0, words * 8, s));
     HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, decode ? 16 : 8, s));         // no bad batch and, decoding, no undecoded batch yet
-    const size_t batches = (r->dimension + r->k - 1) / r->k;
-    if (end == CheckedEnd::Erasures) {
-        SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
-        HIP_TRY(launch_reveal_erasure_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                             r->d_xs.as<uint64_t>(), d_ok, r->d_erase.as<uint64_t>(), r->k, r->job_checks,
-                                             (uint32_t)r->job_rows, max_errors, policy == SDA_CHECK_CORRECT, batches, r->dimension, r->mod,
-                                             r->mont, d_out, d_report, s));
-    } else if (decode)
-        HIP_TRY(launch_reveal_decode_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                            r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows,
-                                            max_errors ? max_errors : r->job_checks / 2, policy == SDA_CHECK_CORRECT, batches, r->dimension,
-                                            r->mod, r->mont, d_out, d_report, s));
-    else
-        HIP_TRY(launch_reveal_check_finish(r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                           r->d_xs.as<uint64_t>(), r->k, r->job_checks, (uint32_t)r->job_rows, policy == SDA_CHECK_CORRECT,
-                                           batches, r->dimension, r->mod, r->mont, d_out, d_report, s));
-    NOTE_CALL_KERNELS("%s", end == CheckedEnd::Erasures ? "reveal_erasure_setup_kernel + reveal_erasure_finish_kernel"
-                            : decode                  ? "reveal_decode_finish_kernel"
-                                                      : "reveal_check_finish_kernel");
+    if (end == RevealEnd::Erasures) SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
+    SDA_TRY(launch_checked_end(r, end, d_ok, max_errors, policy, nullptr, d_out, d_report, s));
     r->job_begun = false;
     r->job_checks = 0;
     return SDA_OK;
@@ -2196,9 +2195,9 @@ static int finish_with_checks(sda_secret_reconstructor* r, CheckedEnd end, const
 // reconstruct_checked / reconstruct_decoded / reconstruct_erasures: host rows through one checked job, the secrets and the report
 // back to the host.  erased (the erasure form only; NULL: none): n_rows host bytes, non-zero = erased
 static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* indices, const int64_t* const* rows, const size_t* row_lens,
-                                   size_t n_rows, unsigned checks, CheckedEnd end, const uint8_t* erased, unsigned max_errors, int policy,
+                                   size_t n_rows, unsigned checks, RevealEnd end, const uint8_t* erased, unsigned max_errors, int policy,
                                    int64_t* out, size_t out_cap, size_t* out_len, uint64_t* report) {
-    const bool decode = end != CheckedEnd::Locate;
+    const bool decode = end != RevealEnd::Locate;
     if (!r || !out_len) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL argument");
     *out_len = 0;
     if (n_rows > 0 && (!rows || !row_lens)) return fail(SDA_ERR_INVALID_ARGUMENT, "NULL rows");
@@ -2206,9 +2205,9 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
     if (n_rows < (size_t)r->t + r->k) return fail_not_enough_shares();
     if (!report) return fail(SDA_ERR_INVALID_ARGUMENT, "report is NULL");
     if (!policy_known(policy)) return fail_policy(policy);
-    if (end == CheckedEnd::Erasures && max_errors > checks / 2)
+    if (end == RevealEnd::Erasures && max_errors > checks / 2)
         return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: at most checks / 2 positions are decoded", checks, max_errors);
-    if (end == CheckedEnd::Decode && (checks < 2 || max_errors > checks / 2))
+    if (end == RevealEnd::Decode && (checks < 2 || max_errors > checks / 2))
         return fail(SDA_ERR_INVALID_ARGUMENT, "checks = %u, max_errors = %u: decoding takes at least 2 checks and at most checks / 2 positions", checks, max_errors);
     const size_t batches = (r->dimension + r->k - 1) / r->k;
     for (size_t i = 0; i < n_rows; ++i)
@@ -2222,7 +2221,7 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
     SDA_TRY(sda_secret_reconstructor_begin_checked_dev(r, indices, n_rows, batches, checks, nullptr));
     SDA_TRY(sda_secret_reconstructor_update_dev(r, 0, r->d_shares.as<int64_t>(), n_rows, stride, nullptr));
     const uint32_t* d_ok = nullptr;
-    if (end == CheckedEnd::Erasures && erased) {
+    if (end == RevealEnd::Erasures && erased) {
         std::vector<uint32_t> ok(n_rows);
         for (size_t i = 0; i < n_rows; ++i) ok[i] = erased[i] ? 0u : 1u;
         SDA_TRY(r->d_flags.reserve(n_rows * 4));
@@ -2240,14 +2239,14 @@ static int reconstruct_with_checks(sda_secret_reconstructor* r, const size_t* in
 
 extern "C" int sda_secret_reconstructor_finish_checked_dev(sda_secret_reconstructor_t* r, int policy, int64_t* d_out, size_t out_cap,
                                                            uint64_t* d_report, void* stream) {
-    return finish_with_checks(r, CheckedEnd::Locate, nullptr, 0, policy, d_out, out_cap, d_report, stream);
+    return finish_with_checks(r, RevealEnd::Locate, nullptr, 0, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, int policy, int64_t* out, size_t out_cap, size_t* out_len,
                                                             uint64_t* report) {
-    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Locate, nullptr, 0, policy, out, out_cap, out_len, report);
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, RevealEnd::Locate, nullptr, 0, policy, out, out_cap, out_len, report);
 }
 
 // ---- the decoding finish: up to floor(checks / 2) faulty positions per batch, from the same syndromes ---------------------------
@@ -2255,14 +2254,14 @@ extern "C" int sda_secret_reconstructor_reconstruct_checked(sda_secret_reconstru
 // whose solution with |E| <= checks / 2 is unique.  The kernel solves it per batch (reveal_decode.hpp); the tables are begin_checked_dev's.
 extern "C" int sda_secret_reconstructor_finish_decoded_dev(sda_secret_reconstructor_t* r, unsigned max_errors, int policy, int64_t* d_out,
                                                            size_t out_cap, uint64_t* d_report, void* stream) {
-    return finish_with_checks(r, CheckedEnd::Decode, nullptr, max_errors, policy, d_out, out_cap, d_report, stream);
+    return finish_with_checks(r, RevealEnd::Decode, nullptr, max_errors, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstructor_t* r, const size_t* indices,
                                                             const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                             unsigned checks, unsigned max_errors, int policy, int64_t* out,
                                                             size_t out_cap, size_t* out_len, uint64_t* report) {
-    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Decode, nullptr, max_errors, policy, out, out_cap, out_len,
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, RevealEnd::Decode, nullptr, max_errors, policy, out, out_cap, out_len,
                                    report);
 }
 
@@ -2273,14 +2272,14 @@ extern "C" int sda_secret_reconstructor_reconstruct_decoded(sda_secret_reconstru
 // S_0 .. S_{f-1}.  d_ok stays on the device: reveal_erasure_setup_kernel reads it, and the host never learns f.
 extern "C" int sda_secret_reconstructor_finish_erasures_dev(sda_secret_reconstructor_t* r, const uint32_t* d_ok, unsigned max_errors,
                                                             int policy, int64_t* d_out, size_t out_cap, uint64_t* d_report, void* stream) {
-    return finish_with_checks(r, CheckedEnd::Erasures, d_ok, max_errors, policy, d_out, out_cap, d_report, stream);
+    return finish_with_checks(r, RevealEnd::Erasures, d_ok, max_errors, policy, d_out, out_cap, d_report, stream);
 }
 
 extern "C" int sda_secret_reconstructor_reconstruct_erasures(sda_secret_reconstructor_t* r, const size_t* indices,
                                                              const int64_t* const* rows, const size_t* row_lens, size_t n_rows,
                                                              unsigned checks, const uint8_t* erased, unsigned max_errors, int policy,
                                                              int64_t* out, size_t out_cap, size_t* out_len, uint64_t* report) {
-    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, CheckedEnd::Erasures, erased, max_errors, policy, out, out_cap,
+    return reconstruct_with_checks(r, indices, rows, row_lens, n_rows, checks, RevealEnd::Erasures, erased, max_errors, policy, out, out_cap,
                                    out_len, report);
 }
 
@@ -2960,7 +2959,7 @@ extern "C" int sda_secret_unmasker_unmask_checked_jobs_dev(sda_secret_unmasker_t
     if (!r->job_begun) return fail(SDA_ERR_STATE, "unmask before the reconstructor's begin");
     if (end != SDA_CHECKED_END_LOCATE && end != SDA_CHECKED_END_DECODE && end != SDA_CHECKED_END_ERASURES)
         return fail(SDA_ERR_INVALID_ARGUMENT, "end = %d: SDA_CHECKED_END_LOCATE, SDA_CHECKED_END_DECODE or SDA_CHECKED_END_ERASURES", end);
-    const CheckedEnd which = end == SDA_CHECKED_END_LOCATE ? CheckedEnd::Locate : end == SDA_CHECKED_END_DECODE ? CheckedEnd::Decode : CheckedEnd::Erasures;
+    const RevealEnd which = end == SDA_CHECKED_END_LOCATE ? RevealEnd::Locate : end == SDA_CHECKED_END_DECODE ? RevealEnd::Decode : RevealEnd::Erasures;
     SDA_TRY(checked_end_refusals(r, which, max_errors, policy, d_out, out_cap, d_report));
     if (has_mask && !mc->core.begun) return fail(SDA_ERR_STATE, "unmask before the mask combiner's begin");
     if (uc.rust_signed || r->job_acc.rust_signed || (has_mask && mc->core.acc.rust_signed))
@@ -2972,24 +2971,16 @@ extern "C" int sda_secret_unmasker_unmask_checked_jobs_dev(sda_secret_unmasker_t
         return fail(SDA_ERR_INVALID_ARGUMENT, "results_pass_bits = %u: 0, or 16 for the caller who repairs refused boxes", results_pass_bits);
     SDA_TRY(r->ctx.use());
     hipStream_t s = r->ctx.pick(stream);
-    const bool decode = which != CheckedEnd::Locate;
+    const bool decode = which != RevealEnd::Locate;
     const size_t words = decode ? sda_reconstruct_decode_report_words(r->job_rows) : sda_reconstruct_report_words(r->job_rows);
-    if (len && which == CheckedEnd::Erasures) SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
+    if (len && which == RevealEnd::Erasures) SDA_TRY(r->d_erase.reserve(reveal_erasure_table_words(r->job_rows) * 8));
     HIP_TRY(hipMemsetAsync(d_report, 0, words * 8, s));
     HIP_TRY(hipMemsetAsync(d_report + 3, 0xFF, decode ? 16 : 8, s));         // as finish_with_checks initialises it
     if (len) {
         const AccState* m = has_mask ? &mc->core.acc : nullptr;
-        const RevealUnmaskEnd kernel = which == CheckedEnd::Locate ? RevealUnmaskEnd::Locate : which == CheckedEnd::Decode ? RevealUnmaskEnd::Decode : RevealUnmaskEnd::Erasures;
-        const uint32_t cap = which == CheckedEnd::Decode && !max_errors ? r->job_checks / 2 : max_errors;
-        HIP_TRY(launch_reveal_unmask_finish(kernel, r->job_acc.lo.as<uint64_t>(), r->job_acc.hi.as<int64_t>(), r->d_corr.as<uint64_t>(),
-                                            r->d_xs.as<uint64_t>(), d_ok, which == CheckedEnd::Erasures ? r->d_erase.as<uint64_t>() : nullptr,
-                                            r->k, r->job_checks, (uint32_t)r->job_rows, cap, policy == SDA_CHECK_CORRECT,
-                                            (r->dimension + r->k - 1) / r->k, r->dimension, r->mod, r->mont, m ? m->lo.as<uint64_t>() : nullptr,
-                                            m ? m->hi.as<int64_t>() : nullptr, has_mask ? mc->core.mod : r->mod, d_status_masks,
-                                            d_status_results, results_pass_bits, d_out, d_report, s));
-        NOTE_CALL_KERNELS("%s", which == CheckedEnd::Erasures ? "reveal_erasure_setup_kernel + reveal_decode_unmask_kernel<true>"
-                                : decode                      ? "reveal_decode_unmask_kernel<false>"
-                                                              : "reveal_check_unmask_kernel");
+        const RevealFinishUnmask unmask{m ? m->lo.as<uint64_t>() : nullptr, m ? m->hi.as<int64_t>() : nullptr, has_mask ? mc->core.mod : r->mod,
+                                        d_status_masks, d_status_results, results_pass_bits};
+        SDA_TRY(launch_checked_end(r, which, d_ok, max_errors, policy, &unmask, d_out, d_report, s));
     }
     if (mc) {                                                                 // as sda_mask_combiner_finish_dev ends its job
         if (has_mask && mc->core.d_seeds.p) HIP_TRY(hipMemsetAsync(mc->core.d_seeds.p, 0, mc->core.d_seeds.cap, s));

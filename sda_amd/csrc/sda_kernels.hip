@@ -1259,21 +1259,29 @@ __global__ __launch_bounds__(kThreads) void unmask_finish_kernel(const uint64_t*
 // The finish of a CHECKED reconstruction job (sda_secret_reconstructor_begin_checked_dev): the job's matrix carried `checks`
 // parity columns behind its k secret columns, so batch b owns the k + checks sums lo/hi[b (k + checks) ..]: its k secrets and
 // the syndromes S_d = sum_i u_i x_i^d share_i[b], which are 0 mod p when the rows of the batch lie on one polynomial of degree
-// <= t + k.  One lane = one batch.  It folds the syndromes (N independent folds step through one loop, as above), and on a
-// non-zero one looks for the positions i with S_{d+1} = x_i S_d for every d < checks - 1 (x in Montgomery form: one REDC per
-// test); exactly one = the batch is located, and under SDA_CHECK_CORRECT its secrets lose (R[s][c] / u_c) S_0.  Then the secrets
-// are folded, up to four at a time, corrected and stored compacted; the padding of the last batch is folded and not stored.
-// Everything indexed by a run-time count is consumed where it is produced (the secrets) or lives in an array whose indices are
-// compile-time constants after unrolling (the 16 syndromes): no scratch.
-// The report: counts are reduced over the wave (ballot + popcount) and the workgroup (LDS) before they reach memory, the blame
+// <= t + k.  One lane = one batch, in every kernel of the family; each is put together from the pieces below:
+//   the lane (reveal_lane) and its folded syndromes (reveal_syndromes; N independent folds step through one loop, as above);
+//   a verdict on a non-zero syndrome - the LOCATING one (reveal_locate: the positions i with S_{d+1} = x_i S_d for every
+//     d < checks - 1, exactly one = located) or the DECODING one (reveal_decode<kErasures>: Berlekamp-Massey, roots, magnitudes,
+//     with kErasures around the positions reveal_erasure_setup_kernel's table marks as erased);
+//   the secrets (reveal_secrets): folded up to four at a time, corrected under SDA_CHECK_CORRECT and stored compacted, either as
+//     they are (StorePlain) or unmasked and gated (StoreUnmasked); the padding of the last batch is folded and not stored;
+//   the report of the verdicts (reveal_report_located, reveal_report_decoded).
+// reveal_check_finish_kernel / reveal_check_unmask_kernel = locating x {plain, unmasked}; reveal_decode_finish_kernel,
+// reveal_erasure_finish_kernel, reveal_decode_unmask_kernel<false | true> = decoding x {no erasures, erasures} x {plain, unmasked}.
+// Everything indexed by a run-time count is consumed where it is produced (the secrets), lives in an array whose indices are
+// compile-time constants after unrolling (the 16 syndromes, the 16 erased magnitudes) or in the lane's own LDS column (the
+// decoded positions and magnitudes): no scratch.
+// The reports: counts are reduced over the wave (ballot + popcount) and the workgroup (LDS) before they reach memory, the blame
 // of a position once per wave for all its lanes that name it - a job whose every batch blames one position issues one global
-// atomic per wave for it, not one per batch.  Sums and a minimum: the report does not depend on the order of arrival.
-struct RevealCheckJob {
+// atomic per wave for it, not one per batch.  Sums, minima and a maximum: a report does not depend on the order of arrival.
+struct RevealJob {
     const uint64_t* lo;          // [batches][k + checks]
     const int64_t* hi;
     const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
     const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
-    uint32_t k, checks, n_rows, correct;
+    const uint64_t* table;       // reveal_erasure_setup_kernel's; nullptr unless erasures are in play
+    uint32_t k, checks, n_rows, correct, cap;   // cap: the decoding verdicts' most positions per batch, not read by the locating one
     uint64_t batches, dimension;
     ModParams mod;
     uint64_t pinv;
@@ -1304,217 +1312,27 @@ static __device__ __forceinline__ void fold_up_to_4(uint32_t n, const uint64_t* 
     else fold_group<1>(lo, hi, live, mod, o);
 }
 
-__global__ __launch_bounds__(kThreads) void reveal_check_finish_kernel(RevealCheckJob J, int64_t* __restrict__ out,
-                                                                       unsigned long long* __restrict__ report) {
-    __shared__ unsigned int wg_count[3];                   // bad, located, corrected batches of this workgroup
-    __shared__ unsigned long long wg_first;
-    if (threadIdx.x == 0) {
-        wg_count[0] = wg_count[1] = wg_count[2] = 0;
-        wg_first = ~0ull;
-    }
-    __syncthreads();
+// this lane's batch and its row of sums; a lane past the last batch is not live, folds zeros and points at batch 0
+struct RevealLane {
+    uint64_t b;
+    bool live;
+    const uint64_t* lo;
+    const int64_t* hi;
+};
+static __device__ __forceinline__ RevealLane reveal_lane(const RevealJob& J) {
     const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const bool live = b < J.batches;
-    const int lane = threadIdx.x & 63;
     const uint32_t width = J.k + J.checks;
-    const uint64_t* lo = J.lo + (live ? b : 0) * width;
-    const int64_t* hi = J.hi + (live ? b : 0) * width;
-    const uint64_t m = J.mod.m;
-
-    uint64_t S[kMaxChecks];
-#pragma unroll
-    for (int g = 0; g < kMaxChecks / 4; ++g) {
-        uint64_t o[4] = {0, 0, 0, 0};
-        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
-    }
-    uint64_t any = 0;
-#pragma unroll
-    for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
-    const bool bad = live && any != 0;
-
-    uint32_t where = 0, fits = 0;
-    if (bad && J.checks >= 2 && S[0] != 0) {
-        for (uint32_t i = 0; i < J.n_rows; ++i) {
-            const uint64_t x = J.xs[i];
-            bool fit = true;
-#pragma unroll
-            for (int d = 0; d + 1 < kMaxChecks; ++d)
-                if ((uint32_t)(d + 1) < J.checks) fit = fit && mont_redc(mul64x64(x, S[d]), m, J.pinv) == S[d + 1];
-            if (fit) { where = i; ++fits; }
-        }
-    }
-    const bool located = fits == 1;
-    const bool fix = located && J.correct != 0;
-
-    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
-        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
-        uint64_t o[4];
-        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t e = b * J.k + s0 + j;
-            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
-            uint64_t v = o[j];
-            if (fix) v = submod(v, mont_redc(mul64x64(J.corr[(uint64_t)(s0 + j) * J.n_rows + where], S[0]), m, J.pinv), m);
-            out[e] = (int64_t)v;
-        }
-    }
-
-    // ---- the report ----
-    const unsigned long long bad_lanes = __ballot(bad), located_lanes = __ballot(located), fixed_lanes = __ballot(fix);
-    if (lane == 0 && bad_lanes != 0) {
-        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
-        if (located_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(located_lanes));
-        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
-        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
-        atomicMin(&wg_first, (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
-    }
-    unsigned long long pending = located_lanes;
-    while (pending) {                                      // one atomic per distinct blamed position of the wave
-        const int leader = __ffsll((long long)pending) - 1;
-        const uint32_t pos = (uint32_t)__shfl((int)where, leader);
-        const unsigned long long same = __ballot(located && where == pos);
-        if (lane == leader) atomicAdd(&report[4 + pos], (unsigned long long)__popcll(same));
-        pending &= ~same;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
-        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
-        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
-        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
-        atomicMin(&report[3], wg_first);
-    }
+    return {b, live, J.lo + (live ? b : 0) * width, J.hi + (live ? b : 0) * width};
 }
 
-// The DECODING finish of a checked job (sda_secret_reconstructor_finish_decoded_dev): the same sums, tables and lane = batch as
-// above, and a clean lane does the same work - fold the syndromes, fold the secrets, store.  A lane with a non-zero syndrome
-// decodes (reveal_decode.hpp): Berlekamp-Massey for the connection polynomial and L; L <= cap and exactly L roots of the reversed
-// polynomial among the job's points = the batch is decoded with nu = L positions, whose magnitudes Y_j = u_i e_i follow from the
-// first L syndromes; under SDA_CHECK_CORRECT its secrets lose sum_j corr[s][i_j] Y_j.  Positions and magnitudes (at most 8 per
-// lane, indexed at run time) live in LDS, each lane in its own column: no scratch, no barrier between a lane's store and load.
-// The report ([16 + n_rows], see sda_hip.h) is reduced like the sibling's: ballots and shuffles only where the whole wave goes,
-// counts per workgroup in LDS, the blame of a position once per wave and error slot for all lanes that name it there.
-struct RevealDecodeJob {
-    const uint64_t* lo;          // [batches][k + checks]
-    const int64_t* hi;
-    const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
-    const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
-    uint32_t k, checks, n_rows, correct, cap;
-    uint64_t batches, dimension;
-    ModParams mod;
-    uint64_t pinv;
-};
-
-__global__ __launch_bounds__(kThreads) void reveal_decode_finish_kernel(RevealDecodeJob J, int64_t* __restrict__ out,
-                                                                        unsigned long long* __restrict__ report) {
-    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
-    __shared__ unsigned int wg_most;                       // the largest nu
-    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
-    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
-    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
-    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        wg_most = 0;
-        wg_first[0] = wg_first[1] = ~0ull;
-    }
-    __syncthreads();
-    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool live = b < J.batches;
-    const int lane = threadIdx.x & 63;
-    const uint32_t width = J.k + J.checks;
-    const uint64_t* lo = J.lo + (live ? b : 0) * width;
-    const int64_t* hi = J.hi + (live ? b : 0) * width;
-    const uint64_t m = J.mod.m;
-
-    uint64_t S[kMaxChecks];
+static __device__ __forceinline__ void reveal_syndromes(const RevealJob& J, const RevealLane& A, uint64_t (&S)[kMaxChecks]) {
 #pragma unroll
     for (int g = 0; g < kMaxChecks / 4; ++g) {
         uint64_t o[4] = {0, 0, 0, 0};
-        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
+        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, A.lo + J.k + 4 * g, A.hi + J.k + 4 * g, A.live, J.mod, o);
 #pragma unroll
         for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
-    }
-    uint64_t any = 0;
-#pragma unroll
-    for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
-    const bool bad = live && any != 0;
-
-    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
-    if (bad) {
-        uint64_t C[kDecodeErrors + 1];
-        const uint32_t L = decode_bm(S, J.checks, m, J.pinv, C);
-        if (L >= 1 && L <= J.cap &&
-            decode_roots(C, J.cap, J.n_rows, J.xs, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L) {
-            uint64_t Om[kDecodeErrors];
-            decode_omega(S, C, J.cap, m, J.pinv, Om);
-            for (uint32_t j = 0; j < L; ++j)
-                dec_y[j][threadIdx.x] = decode_magnitude(C, Om, L, J.xs[dec_pos[j][threadIdx.x]], m, J.pinv);
-            nu = L;
-        }
-    }
-    const bool decoded = nu != 0;
-    const bool fix = decoded && J.correct != 0;
-
-    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
-        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
-        uint64_t o[4];
-        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t e = b * J.k + s0 + j;
-            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
-            uint64_t v = o[j];
-            if (fix) {
-                const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
-                for (uint32_t q = 0; q < nu; ++q)
-                    v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
-            }
-            out[e] = (int64_t)v;
-        }
-    }
-
-    // ---- the report ----
-    const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
-    const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
-    if (lane == 0 && bad_lanes != 0) {
-        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
-        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
-        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
-        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
-        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
-        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
-    }
-    if (decoded_lanes != 0) {                              // wave-uniform
-        for (uint32_t j = 0; j < J.cap; ++j) {
-            const unsigned long long with = __ballot(nu == j + 1);
-            if (lane == 0 && with != 0) {
-                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
-                atomicMax(&wg_most, j + 1);
-            }
-            const bool has = j < nu;
-            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
-            unsigned long long pending = __ballot(has);
-            while (pending) {                              // one atomic per distinct position the wave blames in slot j
-                const int leader = __ffsll((long long)pending) - 1;
-                const uint32_t pos = (uint32_t)__shfl((int)mine, leader);
-                const unsigned long long same = __ballot(has && mine == pos);
-                if (lane == leader) atomicAdd(&report[16 + pos], (unsigned long long)__popcll(same));
-                pending &= ~same;
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
-        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
-        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
-        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
-        atomicMin(&report[3], wg_first[0]);
-        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
-        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
-        for (int j = 0; j < kDecodeErrors; ++j)
-            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
     }
 }
 
@@ -1571,165 +1389,10 @@ __global__ __launch_bounds__(kThreads) void reveal_erasure_setup_kernel(const ui
     for (uint32_t i = tid; i < n_rows; i += kThreads) table[kEraseInv + i] = erase_inv_gamma(gam, f, xs[i], p, pinv);
 }
 
-// Part 2, one lane per batch with the structure of reveal_decode_finish_kernel.  f and the overflow word are read from the table
-// (wave-uniform, as every table entry but 1 / Gamma at a located position).  The lane folds S, folds the f erased points into a
-// copy T and keeps T_0 .. T_{c-f-1}: all zero = the batch is consistent, else bad, and T is decoded with at most
-// min(cap, floor((c - f) / 2)) non-erased positions, Y = Z / Gamma(x).  Under SDA_CHECK_CORRECT a consistent or decoded batch
-// with a non-zero S takes its errors out of S_0 .. S_{f-1}, solves the erased magnitudes by f dot products - they stay in sixteen
-// registers walked by unrolled loops, the erased positions are the table's - and its secrets lose the correction over E u F.
-// Located positions and magnitudes live in LDS columns as in the sibling: no scratch.  On overflow the lane folds and stores.
-struct RevealErasureJob {
-    const uint64_t* lo;          // [batches][k + checks]
-    const int64_t* hi;
-    const uint64_t* corr;        // [k][n_rows]: R[s][i] / u_i, Montgomery form
-    const uint64_t* xs;          // [n_rows]: the evaluation points, Montgomery form
-    const uint64_t* table;       // reveal_erasure_setup_kernel's
-    uint32_t k, checks, n_rows, correct, cap;
-    uint64_t batches, dimension;
-    ModParams mod;
-    uint64_t pinv;
-};
-
-__global__ __launch_bounds__(kThreads) void reveal_erasure_finish_kernel(RevealErasureJob J, int64_t* __restrict__ out,
-                                                                         unsigned long long* __restrict__ report) {
-    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
-    __shared__ unsigned int wg_most;                       // the largest nu
-    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
-    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
-    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
-    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        wg_most = 0;
-        wg_first[0] = wg_first[1] = ~0ull;
-    }
-    __syncthreads();
-    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool live = b < J.batches;
-    const int lane = threadIdx.x & 63;
-    const uint32_t width = J.k + J.checks;
-    const uint64_t* lo = J.lo + (live ? b : 0) * width;
-    const int64_t* hi = J.hi + (live ? b : 0) * width;
-    const uint64_t m = J.mod.m;
-    const bool over = J.table[kEraseOver] != 0;
-    const uint32_t f = over ? 0 : (uint32_t)J.table[kEraseCount];             // <= checks from here on
-    const uint32_t len = J.checks - f;                                         // the modified syndromes
-    const uint32_t cap = J.cap < len / 2 ? J.cap : len / 2;
-
-    uint64_t S[kMaxChecks], T[kMaxChecks];
-#pragma unroll
-    for (int g = 0; g < kMaxChecks / 4; ++g) {
-        uint64_t o[4] = {0, 0, 0, 0};
-        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[4 * g + j] = T[4 * g + j] = o[j];        // 0 from J.checks on
-    }
-#pragma unroll 1
-    for (uint32_t q = 0; q < f; ++q) erase_fold_point(T, J.checks, J.xs[J.table[kErasePos + q]], m, J.pinv);
-    erase_keep(T, len);
-    uint64_t any = 0, any_s = 0;
-#pragma unroll
-    for (int d = 0; d < kMaxChecks; ++d) {
-        any |= T[d];
-        any_s |= S[d];
-    }
-    const bool bad = live && !over && any != 0;
-
-    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
-    if (bad && cap >= 1) {
-        uint64_t C[kDecodeErrors + 1];
-        const uint32_t L = decode_bm(T, len, m, J.pinv, C);
-        if (L >= 1 && L <= cap &&
-            decode_roots_live(C, cap, J.n_rows, J.xs, J.table + kEraseInv, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L) {
-            uint64_t Om[kDecodeErrors];
-            decode_omega(T, C, cap, m, J.pinv, Om);
-            for (uint32_t j = 0; j < L; ++j) {
-                const uint32_t at = dec_pos[j][threadIdx.x];
-                const uint64_t Z = decode_magnitude(C, Om, L, J.xs[at], m, J.pinv);
-                dec_y[j][threadIdx.x] = dec_mm(Z, J.table[kEraseInv + at], m, J.pinv);
-            }
-            nu = L;
-        }
-    }
-    const bool decoded = nu != 0;
-    const bool fix = decoded && J.correct != 0;
-    // the erased positions' share: a consistent or decoded batch whose sums are not all zero
-    const bool mend = live && f != 0 && J.correct != 0 && any_s != 0 && (!bad || decoded);
-    uint64_t Ye[kEraseMax];
-#pragma unroll
-    for (int j = 0; j < kEraseMax; ++j) Ye[j] = 0;
-    if (mend) {
-        for (uint32_t q = 0; q < nu; ++q) erase_remove(S, f, dec_y[q][threadIdx.x], J.xs[dec_pos[q][threadIdx.x]], m, J.pinv);
-        erase_magnitudes(S, f, J.table + kEraseRows, m, J.pinv, Ye);
-    }
-
-    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
-        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
-        uint64_t o[4];
-        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t e = b * J.k + s0 + j;
-            if (!live || (uint32_t)j >= n || e >= J.dimension) continue;          // batched.rs:94: the padding is not stored
-            uint64_t v = o[j];
-            const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
-            if (fix) {
-                for (uint32_t q = 0; q < nu; ++q)
-                    v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
-            }
-            if (mend) v = erase_apply(v, corr, J.table, f, Ye, m, J.pinv);
-            out[e] = (int64_t)v;
-        }
-    }
-
-    // ---- the report: the sibling's ----
-    const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
-    const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
-    if (lane == 0 && bad_lanes != 0) {
-        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
-        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
-        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
-        // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
-        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
-        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
-    }
-    if (decoded_lanes != 0) {                              // wave-uniform
-        for (uint32_t j = 0; j < cap; ++j) {
-            const unsigned long long with = __ballot(nu == j + 1);
-            if (lane == 0 && with != 0) {
-                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
-                atomicMax(&wg_most, j + 1);
-            }
-            const bool has = j < nu;
-            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
-            unsigned long long pending = __ballot(has);
-            while (pending) {                              // one atomic per distinct position the wave blames in slot j
-                const int leader = __ffsll((long long)pending) - 1;
-                const uint32_t pos = (uint32_t)__shfl((int)mine, leader);
-                const unsigned long long same = __ballot(has && mine == pos);
-                if (lane == leader) atomicAdd(&report[16 + pos], (unsigned long long)__popcll(same));
-                pending &= ~same;
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
-        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
-        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
-        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
-        atomicMin(&report[3], wg_first[0]);
-        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
-        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
-        for (int j = 0; j < kDecodeErrors; ++j)
-            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
-    }
-}
-
-// The UNMASKING forms of the three finishes (sda_secret_unmasker_unmask_checked_jobs_dev): the same lane = batch, the same
-// verdicts and the same report, and where the finishes store a corrected secret v these store (canonical(v, q_mask) - fold of the
-// mask job's sum, q_mask) mod q_mask, as unmask_finish_kernel does for a plain job - the masked output and the combined mask
-// never reach memory.  They stand BESIDE the three kernels above, whose text and code they leave alone: those are measured
-// products.  The locating form is its own kernel; the decoding and the erasure form are the two instances of one template, the
-// erasure steps under `if constexpr`.
+// The UNMASKING store of the family (sda_secret_unmasker_unmask_checked_jobs_dev): where a plain finish stores a corrected secret
+// v, the unmasking form of the same end stores (canonical(v, q_mask) - fold of the mask job's sum, q_mask) mod q_mask, as
+// unmask_finish_kernel does for a plain job - the masked output and the combined mask never reach memory.  Verdicts and report
+// are the plain form's, whatever the gate says.
 struct RevealUnmask {
     const uint64_t* m_lo;        // [dimension]: the mask job's sums - NOT batches * k; nullptr: no mask, the store is v (none.rs:28-33)
     const int64_t* m_hi;
@@ -1792,37 +1455,54 @@ static __device__ __forceinline__ uint32_t unmask_group_have(bool live, uint64_t
     return dimension - e0 < n ? (uint32_t)(dimension - e0) : n;
 }
 
-__global__ __launch_bounds__(kThreads) void reveal_check_unmask_kernel(RevealCheckJob J, RevealUnmask U, int64_t* __restrict__ out,
-                                                                       unsigned long long* __restrict__ report) {
-    __shared__ unsigned int wg_count[3];                   // bad, located, corrected batches of this workgroup
-    __shared__ unsigned long long wg_first;
-    if (threadIdx.x == 0) {
-        wg_count[0] = wg_count[1] = wg_count[2] = 0;
-        wg_first = ~0ull;
+// the two stores of a group of corrected secrets, v[j] for j < have
+struct StorePlain {
+    __device__ __forceinline__ void operator()(uint32_t, uint64_t e0, uint32_t have, uint64_t (&v)[4], int64_t* __restrict__ out) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if ((uint32_t)j < have) out[e0 + j] = (int64_t)v[j];               // batched.rs:94: the padding is not stored
     }
-    __syncthreads();
-    const bool shut = unmask_gate_shut(U);
-    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool live = b < J.batches;
-    const int lane = threadIdx.x & 63;
-    const uint32_t width = J.k + J.checks;
-    const uint64_t* lo = J.lo + (live ? b : 0) * width;
-    const int64_t* hi = J.hi + (live ? b : 0) * width;
-    const uint64_t m = J.mod.m;
+};
+struct StoreUnmasked {
+    const RevealUnmask& U;
+    bool shut;
+    __device__ __forceinline__ void operator()(uint32_t n, uint64_t e0, uint32_t have, uint64_t (&v)[4], int64_t* __restrict__ out) const {
+        unmask_store_group(U, shut, n, e0, have, v, out);
+    }
+};
 
-    uint64_t S[kMaxChecks];
+// The secrets of this lane's batch: folded up to four at a time and handed to `store`.  When `amend` is set (a verdict that
+// corrects), amended(s, v) is the corrected value of secret s - under the sharing modulus, before any canonicalisation under q_mask
+template <class Amended, class Store>
+static __device__ __forceinline__ void reveal_secrets(const RevealJob& J, const RevealLane& A, bool amend, const Amended& amended,
+                                                      const Store& store, int64_t* __restrict__ out) {
+    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
+        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
+        uint64_t o[4];
+        fold_up_to_4(n, A.lo + s0, A.hi + s0, A.live, J.mod, o);
+        const uint64_t e0 = A.b * J.k + s0;
+        const uint32_t have = unmask_group_have(A.live, e0, n, J.dimension);
+        if (amend) {
 #pragma unroll
-    for (int g = 0; g < kMaxChecks / 4; ++g) {
-        uint64_t o[4] = {0, 0, 0, 0};
-        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[4 * g + j] = o[j];   // 0 from J.checks on
+            for (int j = 0; j < 4; ++j)
+                if ((uint32_t)j < have) o[j] = amended(s0 + j, o[j]);
+        }
+        store(n, e0, have, o, out);
     }
+}
+
+// ---- the LOCATING end (sda_secret_reconstructor_finish_checked_dev): on a non-zero syndrome the positions i with
+// S_{d+1} = x_i S_d for every d < checks - 1 (x in Montgomery form: one REDC per test); exactly one = the batch is located, and
+// under SDA_CHECK_CORRECT its secrets lose (R[s][c] / u_c) S_0.  checks == 1 locates nothing
+struct RevealLocated {
+    bool bad, located, fix;
+    uint32_t where;
+};
+static __device__ __forceinline__ RevealLocated reveal_locate(const RevealJob& J, const RevealLane& A, const uint64_t (&S)[kMaxChecks]) {
     uint64_t any = 0;
 #pragma unroll
     for (int d = 0; d < kMaxChecks; ++d) any |= S[d];
-    const bool bad = live && any != 0;
-
+    const bool bad = A.live && any != 0;
     uint32_t where = 0, fits = 0;
     if (bad && J.checks >= 2 && S[0] != 0) {
         for (uint32_t i = 0; i < J.n_rows; ++i) {
@@ -1830,77 +1510,104 @@ __global__ __launch_bounds__(kThreads) void reveal_check_unmask_kernel(RevealChe
             bool fit = true;
 #pragma unroll
             for (int d = 0; d + 1 < kMaxChecks; ++d)
-                if ((uint32_t)(d + 1) < J.checks) fit = fit && mont_redc(mul64x64(x, S[d]), m, J.pinv) == S[d + 1];
+                if ((uint32_t)(d + 1) < J.checks) fit = fit && mont_redc(mul64x64(x, S[d]), J.mod.m, J.pinv) == S[d + 1];
             if (fit) { where = i; ++fits; }
         }
     }
     const bool located = fits == 1;
-    const bool fix = located && J.correct != 0;
+    return {bad, located, located && J.correct != 0, where};
+}
 
-    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
-        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
-        uint64_t o[4];
-        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
-        const uint64_t e0 = b * J.k + s0;
-        const uint32_t have = unmask_group_have(live, e0, n, J.dimension);
-        if (fix) {                                         // under the sharing modulus, before the canonicalisation under q_mask
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if ((uint32_t)j < have)
-                    o[j] = submod(o[j], mont_redc(mul64x64(J.corr[(uint64_t)(s0 + j) * J.n_rows + where], S[0]), m, J.pinv), m);
-        }
-        unmask_store_group(U, shut, n, e0, have, o, out);
+// report [4 + n_rows]: bad, located, corrected batches, first bad batch, batches that blame position i
+struct LocatedTally {
+    unsigned long long first;
+    unsigned int count[3];                                 // bad, located, corrected batches of this workgroup
+};
+static __device__ __forceinline__ void reveal_tally_open(LocatedTally& wg) {
+    if (threadIdx.x == 0) {
+        wg.count[0] = wg.count[1] = wg.count[2] = 0;
+        wg.first = ~0ull;
     }
-
-    // ---- the report: reveal_check_finish_kernel's, whatever the gate says ----
-    const unsigned long long bad_lanes = __ballot(bad), located_lanes = __ballot(located), fixed_lanes = __ballot(fix);
+    __syncthreads();
+}
+static __device__ __forceinline__ void reveal_report_located(LocatedTally& wg, const RevealLane& A, const RevealLocated& V,
+                                                             unsigned long long* __restrict__ report) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long bad_lanes = __ballot(V.bad), located_lanes = __ballot(V.located), fixed_lanes = __ballot(V.fix);
     if (lane == 0 && bad_lanes != 0) {
-        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
-        if (located_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(located_lanes));
-        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        atomicAdd(&wg.count[0], (unsigned)__popcll(bad_lanes));
+        if (located_lanes) atomicAdd(&wg.count[1], (unsigned)__popcll(located_lanes));
+        if (fixed_lanes) atomicAdd(&wg.count[2], (unsigned)__popcll(fixed_lanes));
         // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
-        atomicMin(&wg_first, (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+        atomicMin(&wg.first, (unsigned long long)(A.b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
     }
     unsigned long long pending = located_lanes;
     while (pending) {                                      // one atomic per distinct blamed position of the wave
         const int leader = __ffsll((long long)pending) - 1;
-        const uint32_t pos = (uint32_t)__shfl((int)where, leader);
-        const unsigned long long same = __ballot(located && where == pos);
+        const uint32_t pos = (uint32_t)__shfl((int)V.where, leader);
+        const unsigned long long same = __ballot(V.located && V.where == pos);
         if (lane == leader) atomicAdd(&report[4 + pos], (unsigned long long)__popcll(same));
         pending &= ~same;
     }
     __syncthreads();
-    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
-        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
-        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
-        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
-        atomicMin(&report[3], wg_first);
+    if (threadIdx.x == 0 && wg.count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg.count[0]);
+        if (wg.count[1]) atomicAdd(&report[1], (unsigned long long)wg.count[1]);
+        if (wg.count[2]) atomicAdd(&report[2], (unsigned long long)wg.count[2]);
+        atomicMin(&report[3], wg.first);
     }
 }
 
-// kErasures false: reveal_decode_finish_kernel's verdicts (J.table is not read, J.cap is the caller's cap); true:
-// reveal_erasure_finish_kernel's around the table's erased positions
+template <class Store>
+static __device__ __forceinline__ void reveal_locating_finish(const RevealJob& J, const Store& store, int64_t* __restrict__ out,
+                                                              unsigned long long* __restrict__ report) {
+    __shared__ LocatedTally wg;
+    reveal_tally_open(wg);
+    const RevealLane A = reveal_lane(J);
+    uint64_t S[kMaxChecks];
+    reveal_syndromes(J, A, S);
+    const RevealLocated V = reveal_locate(J, A, S);
+    reveal_secrets(J, A, V.fix, [&](uint32_t s, uint64_t v) __attribute__((always_inline)) {
+        return submod(v, mont_redc(mul64x64(J.corr[(uint64_t)s * J.n_rows + V.where], S[0]), J.mod.m, J.pinv), J.mod.m);
+    }, store, out);
+    reveal_report_located(wg, A, V, report);
+}
+
+__global__ __launch_bounds__(kThreads) void reveal_check_finish_kernel(RevealJob J, int64_t* __restrict__ out,
+                                                                       unsigned long long* __restrict__ report) {
+    reveal_locating_finish(J, StorePlain{}, out, report);
+}
+__global__ __launch_bounds__(kThreads) void reveal_check_unmask_kernel(RevealJob J, RevealUnmask U, int64_t* __restrict__ out,
+                                                                       unsigned long long* __restrict__ report) {
+    reveal_locating_finish(J, StoreUnmasked{U, unmask_gate_shut(U)}, out, report);
+}
+
+// ---- the DECODING ends (sda_secret_reconstructor_finish_decoded_dev, _finish_erasures_dev): a clean lane does the locating
+// end's work - fold the syndromes, fold the secrets, store.  A lane with a non-zero syndrome decodes (reveal_decode.hpp):
+// Berlekamp-Massey for the connection polynomial and L; L <= cap and exactly L roots of the reversed polynomial among the job's
+// points = the batch is decoded with nu = L positions, whose magnitudes Y_j = u_i e_i follow from the first L syndromes; under
+// SDA_CHECK_CORRECT its secrets lose sum_j corr[s][i_j] Y_j.  Positions and magnitudes (at most 8 per lane, indexed at run time)
+// live in LDS, each lane in its own column: no scratch, no barrier between a lane's store and load.
+// kErasures (J.table is the setup kernel's): f and the overflow word are read from the table (wave-uniform, as every table entry
+// but 1 / Gamma at a located position).  The lane folds the f erased points into a copy T of S and keeps T_0 .. T_{c-f-1}: all
+// zero = the batch is consistent, else bad, and T is decoded with at most min(cap, floor((c - f) / 2)) non-erased positions,
+// Y = Z / Gamma(x).  Under SDA_CHECK_CORRECT a consistent or decoded batch with a non-zero S takes its errors out of
+// S_0 .. S_{f-1}, solves the erased magnitudes by f dot products - they stay in sixteen registers walked by unrolled loops, the
+// erased positions are the table's - and its secrets lose the correction over E u F.  On overflow the lane folds and stores.
+// Without kErasures T is S, f is 0 and cap is the caller's
+struct DecodeColumns {
+    uint64_t y[kDecodeErrors][kThreads];
+    uint16_t pos[kDecodeErrors][kThreads];
+};
 template <bool kErasures>
-__global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealErasureJob J, RevealUnmask U, int64_t* __restrict__ out,
-                                                                        unsigned long long* __restrict__ report) {
-    __shared__ unsigned int wg_count[3 + kDecodeErrors];   // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
-    __shared__ unsigned int wg_most;                       // the largest nu
-    __shared__ unsigned long long wg_first[2];             // first bad, first undecoded batch
-    __shared__ uint16_t dec_pos[kDecodeErrors][kThreads];
-    __shared__ uint64_t dec_y[kDecodeErrors][kThreads];
-    if (threadIdx.x < 3 + kDecodeErrors) wg_count[threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        wg_most = 0;
-        wg_first[0] = wg_first[1] = ~0ull;
-    }
-    __syncthreads();
-    const bool shut = unmask_gate_shut(U);
-    const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool live = b < J.batches;
-    const int lane = threadIdx.x & 63;
-    const uint32_t width = J.k + J.checks;
-    const uint64_t* lo = J.lo + (live ? b : 0) * width;
-    const int64_t* hi = J.hi + (live ? b : 0) * width;
+struct RevealDecoded {
+    bool bad, decoded, fix, mend;                          // mend: the erased positions take a share of the correction
+    uint32_t nu, f, cap;                                   // nu 1 .. cap: decoded with that many positions
+    uint64_t Ye[kErasures ? kEraseMax : 1];                // the erased magnitudes
+};
+template <bool kErasures>
+static __device__ __forceinline__ void reveal_decode(const RevealJob& J, const RevealLane& A, uint64_t (&S)[kMaxChecks], DecodeColumns& col,
+                                                     RevealDecoded<kErasures>& V) {
     const uint64_t m = J.mod.m;
     bool over = false;
     uint32_t f = 0;                                        // the erased positions, <= checks
@@ -1911,14 +1618,9 @@ __global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealEr
     const uint32_t len = J.checks - f;                     // the (modified) syndromes that are decoded
     const uint32_t cap = kErasures ? (J.cap < len / 2 ? J.cap : len / 2) : J.cap;
 
-    uint64_t S[kMaxChecks], T[kMaxChecks];                 // kErasures false: T is S
+    uint64_t T[kMaxChecks];
 #pragma unroll
-    for (int g = 0; g < kMaxChecks / 4; ++g) {
-        uint64_t o[4] = {0, 0, 0, 0};
-        if ((uint32_t)(4 * g) < J.checks) fold_up_to_4(J.checks - 4 * g, lo + J.k + 4 * g, hi + J.k + 4 * g, live, J.mod, o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) S[4 * g + j] = T[4 * g + j] = o[j];        // 0 from J.checks on
-    }
+    for (int d = 0; d < kMaxChecks; ++d) T[d] = S[d];
     if constexpr (kErasures) {
 #pragma unroll 1
         for (uint32_t q = 0; q < f; ++q) erase_fold_point(T, J.checks, J.xs[J.table[kErasePos + q]], m, J.pinv);
@@ -1930,90 +1632,88 @@ __global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealEr
         any |= T[d];
         any_s |= S[d];
     }
-    const bool bad = live && !over && any != 0;
+    const bool bad = A.live && !over && any != 0;
 
-    uint32_t nu = 0;                                       // 1 .. cap: decoded with that many positions
+    uint32_t nu = 0;
     if (bad && cap >= 1) {
         uint64_t C[kDecodeErrors + 1];
         const uint32_t L = decode_bm(T, len, m, J.pinv, C);
         bool rooted = false;
         if (L >= 1 && L <= cap) {
             if constexpr (kErasures)
-                rooted = decode_roots_live(C, cap, J.n_rows, J.xs, J.table + kEraseInv, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L;
+                rooted = decode_roots_live(C, cap, J.n_rows, J.xs, J.table + kEraseInv, m, J.pinv, &col.pos[0][threadIdx.x], (uint32_t)kThreads) == L;
             else
-                rooted = decode_roots(C, cap, J.n_rows, J.xs, m, J.pinv, &dec_pos[0][threadIdx.x], (uint32_t)kThreads) == L;
+                rooted = decode_roots(C, cap, J.n_rows, J.xs, m, J.pinv, &col.pos[0][threadIdx.x], (uint32_t)kThreads) == L;
         }
         if (rooted) {
             uint64_t Om[kDecodeErrors];
             decode_omega(T, C, cap, m, J.pinv, Om);
             for (uint32_t j = 0; j < L; ++j) {
-                const uint32_t at = dec_pos[j][threadIdx.x];
+                const uint32_t at = col.pos[j][threadIdx.x];
                 uint64_t Y = decode_magnitude(C, Om, L, J.xs[at], m, J.pinv);
                 if constexpr (kErasures) Y = dec_mm(Y, J.table[kEraseInv + at], m, J.pinv);
-                dec_y[j][threadIdx.x] = Y;
+                col.y[j][threadIdx.x] = Y;
             }
             nu = L;
         }
     }
-    const bool decoded = nu != 0;
-    const bool fix = decoded && J.correct != 0;
+    V.bad = bad;
+    V.decoded = nu != 0;
+    V.fix = V.decoded && J.correct != 0;
     // the erased positions' share: a consistent or decoded batch whose sums are not all zero
-    const bool mend = kErasures && live && f != 0 && J.correct != 0 && any_s != 0 && (!bad || decoded);
-    uint64_t Ye[kEraseMax];
+    V.mend = kErasures && A.live && f != 0 && J.correct != 0 && any_s != 0 && (!bad || V.decoded);
+    V.nu = nu;
+    V.f = f;
+    V.cap = cap;
     if constexpr (kErasures) {
 #pragma unroll
-        for (int j = 0; j < kEraseMax; ++j) Ye[j] = 0;
-        if (mend) {
-            for (uint32_t q = 0; q < nu; ++q) erase_remove(S, f, dec_y[q][threadIdx.x], J.xs[dec_pos[q][threadIdx.x]], m, J.pinv);
-            erase_magnitudes(S, f, J.table + kEraseRows, m, J.pinv, Ye);
+        for (int j = 0; j < kEraseMax; ++j) V.Ye[j] = 0;
+        if (V.mend) {
+            for (uint32_t q = 0; q < nu; ++q) erase_remove(S, f, col.y[q][threadIdx.x], J.xs[col.pos[q][threadIdx.x]], m, J.pinv);
+            erase_magnitudes(S, f, J.table + kEraseRows, m, J.pinv, V.Ye);
         }
     }
+}
 
-    for (uint32_t s0 = 0; s0 < J.k; s0 += 4) {
-        const uint32_t n = J.k - s0 < 4 ? J.k - s0 : 4;
-        uint64_t o[4];
-        fold_up_to_4(n, lo + s0, hi + s0, live, J.mod, o);
-        const uint64_t e0 = b * J.k + s0;
-        const uint32_t have = unmask_group_have(live, e0, n, J.dimension);
-        if (fix || mend) {                                 // under the sharing modulus, before the canonicalisation under q_mask
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if ((uint32_t)j >= have) continue;
-                uint64_t v = o[j];
-                const uint64_t* corr = J.corr + (uint64_t)(s0 + j) * J.n_rows;
-                if (fix) {
-                    for (uint32_t q = 0; q < nu; ++q)
-                        v = submod(v, mont_redc(mul64x64(corr[dec_pos[q][threadIdx.x]], dec_y[q][threadIdx.x]), m, J.pinv), m);
-                }
-                if constexpr (kErasures) {
-                    if (mend) v = erase_apply(v, corr, J.table, f, Ye, m, J.pinv);
-                }
-                o[j] = v;
-            }
-        }
-        unmask_store_group(U, shut, n, e0, have, o, out);
+// report [16 + n_rows] (sda_hip.h): bad, decoded, corrected batches, first bad, first undecoded batch, largest nu, the setup
+// kernel's two words, batches decoded with nu = 1 .. 8, batches that blame position i.  Ballots and shuffles only where the
+// whole wave goes, the blame of a position once per wave and error slot for all lanes that name it there
+struct DecodedTally {
+    unsigned long long first[2];                           // first bad, first undecoded batch
+    unsigned int count[3 + kDecodeErrors];                 // bad, decoded, corrected batches of this workgroup; decoded with nu = 1 .. 8
+    unsigned int most;                                     // the largest nu
+};
+static __device__ __forceinline__ void reveal_tally_open(DecodedTally& wg) {
+    if (threadIdx.x < 3 + kDecodeErrors) wg.count[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        wg.most = 0;
+        wg.first[0] = wg.first[1] = ~0ull;
     }
-
-    // ---- the report: the two finishes', whatever the gate says ----
+    __syncthreads();
+}
+static __device__ __forceinline__ void reveal_report_decoded(DecodedTally& wg, const DecodeColumns& col, const RevealLane& A, bool bad,
+                                                             bool decoded, bool fix, uint32_t nu, uint32_t cap,
+                                                             unsigned long long* __restrict__ report) {
+    const int lane = threadIdx.x & 63;
     const unsigned long long bad_lanes = __ballot(bad), decoded_lanes = __ballot(decoded), fixed_lanes = __ballot(fix);
     const unsigned long long lost_lanes = bad_lanes & ~decoded_lanes;
     if (lane == 0 && bad_lanes != 0) {
-        atomicAdd(&wg_count[0], (unsigned)__popcll(bad_lanes));
-        if (decoded_lanes) atomicAdd(&wg_count[1], (unsigned)__popcll(decoded_lanes));
-        if (fixed_lanes) atomicAdd(&wg_count[2], (unsigned)__popcll(fixed_lanes));
+        atomicAdd(&wg.count[0], (unsigned)__popcll(bad_lanes));
+        if (decoded_lanes) atomicAdd(&wg.count[1], (unsigned)__popcll(decoded_lanes));
+        if (fixed_lanes) atomicAdd(&wg.count[2], (unsigned)__popcll(fixed_lanes));
         // lanes hold ascending batches: the first bad lane holds the wave's first bad batch
-        atomicMin(&wg_first[0], (unsigned long long)(b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
-        if (lost_lanes) atomicMin(&wg_first[1], (unsigned long long)(b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
+        atomicMin(&wg.first[0], (unsigned long long)(A.b + (uint64_t)(__ffsll((long long)bad_lanes) - 1)));
+        if (lost_lanes) atomicMin(&wg.first[1], (unsigned long long)(A.b + (uint64_t)(__ffsll((long long)lost_lanes) - 1)));
     }
     if (decoded_lanes != 0) {                              // wave-uniform
         for (uint32_t j = 0; j < cap; ++j) {
             const unsigned long long with = __ballot(nu == j + 1);
             if (lane == 0 && with != 0) {
-                atomicAdd(&wg_count[3 + j], (unsigned)__popcll(with));
-                atomicMax(&wg_most, j + 1);
+                atomicAdd(&wg.count[3 + j], (unsigned)__popcll(with));
+                atomicMax(&wg.most, j + 1);
             }
             const bool has = j < nu;
-            const uint32_t mine = has ? dec_pos[j][threadIdx.x] : 0;
+            const uint32_t mine = has ? col.pos[j][threadIdx.x] : 0;
             unsigned long long pending = __ballot(has);
             while (pending) {                              // one atomic per distinct position the wave blames in slot j
                 const int leader = __ffsll((long long)pending) - 1;
@@ -2025,17 +1725,57 @@ __global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealEr
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0 && wg_count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
-        atomicAdd(&report[0], (unsigned long long)wg_count[0]);
-        if (wg_count[1]) atomicAdd(&report[1], (unsigned long long)wg_count[1]);
-        if (wg_count[2]) atomicAdd(&report[2], (unsigned long long)wg_count[2]);
-        atomicMin(&report[3], wg_first[0]);
-        if (wg_first[1] != ~0ull) atomicMin(&report[4], wg_first[1]);
-        if (wg_most) atomicMax(&report[5], (unsigned long long)wg_most);
+    if (threadIdx.x == 0 && wg.count[0] != 0) {            // one set of atomics per workgroup that saw a bad batch
+        atomicAdd(&report[0], (unsigned long long)wg.count[0]);
+        if (wg.count[1]) atomicAdd(&report[1], (unsigned long long)wg.count[1]);
+        if (wg.count[2]) atomicAdd(&report[2], (unsigned long long)wg.count[2]);
+        atomicMin(&report[3], wg.first[0]);
+        if (wg.first[1] != ~0ull) atomicMin(&report[4], wg.first[1]);
+        if (wg.most) atomicMax(&report[5], (unsigned long long)wg.most);
         for (int j = 0; j < kDecodeErrors; ++j)
-            if (wg_count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg_count[3 + j]);
+            if (wg.count[3 + j]) atomicAdd(&report[8 + j], (unsigned long long)wg.count[3 + j]);
     }
 }
+
+template <bool kErasures, class Store>
+static __device__ __forceinline__ void reveal_decoding_finish(const RevealJob& J, const Store& store, int64_t* __restrict__ out,
+                                                              unsigned long long* __restrict__ report) {
+    __shared__ DecodedTally wg;
+    __shared__ DecodeColumns col;
+    reveal_tally_open(wg);
+    const RevealLane A = reveal_lane(J);
+    uint64_t S[kMaxChecks];
+    reveal_syndromes(J, A, S);
+    RevealDecoded<kErasures> V;
+    reveal_decode<kErasures>(J, A, S, col, V);
+    reveal_secrets(J, A, V.fix || V.mend, [&](uint32_t s, uint64_t v) __attribute__((always_inline)) {
+        const uint64_t* corr = J.corr + (uint64_t)s * J.n_rows;
+        if (V.fix) {
+            for (uint32_t q = 0; q < V.nu; ++q)
+                v = submod(v, mont_redc(mul64x64(corr[col.pos[q][threadIdx.x]], col.y[q][threadIdx.x]), J.mod.m, J.pinv), J.mod.m);
+        }
+        if constexpr (kErasures) {
+            if (V.mend) v = erase_apply(v, corr, J.table, V.f, V.Ye, J.mod.m, J.pinv);
+        }
+        return v;
+    }, store, out);
+    reveal_report_decoded(wg, col, A, V.bad, V.decoded, V.fix, V.nu, V.cap, report);
+}
+
+__global__ __launch_bounds__(kThreads) void reveal_decode_finish_kernel(RevealJob J, int64_t* __restrict__ out,
+                                                                        unsigned long long* __restrict__ report) {
+    reveal_decoding_finish<false>(J, StorePlain{}, out, report);
+}
+__global__ __launch_bounds__(kThreads) void reveal_erasure_finish_kernel(RevealJob J, int64_t* __restrict__ out,
+                                                                         unsigned long long* __restrict__ report) {
+    reveal_decoding_finish<true>(J, StorePlain{}, out, report);
+}
+template <bool kErasures>
+__global__ __launch_bounds__(kThreads) void reveal_decode_unmask_kernel(RevealJob J, RevealUnmask U, int64_t* __restrict__ out,
+                                                                        unsigned long long* __restrict__ report) {
+    reveal_decoding_finish<kErasures>(J, StoreUnmasked{U, unmask_gate_shut(U)}, out, report);
+}
+
 
 // =================================================================================================
 // K4  packed reconstruct: secrets[k] = R[k x n'] * sums[n'] per batch (R in Montgomery form).
@@ -3042,85 +2782,43 @@ hipError_t launch_unmask_finish(const uint64_t* d_recon_lo, const int64_t* d_rec
     return hipGetLastError();
 }
 
-hipError_t launch_reveal_check_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                      uint32_t k, uint32_t checks, uint32_t n_rows, bool correct, size_t batches, size_t dimension,
-                                      const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
-    if (batches == 0) return hipSuccess;
-    if (checks == 0 || checks > (uint32_t)kMaxChecks) return hipErrorInvalidValue;
-    const uint64_t blocks = ceil_div(batches, kThreads);
-    if (hipError_t e = grid_check(blocks)) return e;
-    const RevealCheckJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, batches, dimension, mod, mont.pinv};
-    reveal_check_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
-    return hipGetLastError();
-}
-
-hipError_t launch_reveal_decode_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                       uint32_t k, uint32_t checks, uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches,
-                                       size_t dimension, const ModParams& mod, const MontParams& mont, int64_t* d_out, uint64_t* d_report,
-                                       hipStream_t s) {
-    if (batches == 0) return hipSuccess;
-    if (checks < 2 || checks > (uint32_t)kMaxChecks || max_errors == 0 || max_errors > checks / 2 || n_rows > 65535)   // dec_pos is 16 bits wide
-        return hipErrorInvalidValue;
-    const uint64_t blocks = ceil_div(batches, kThreads);
-    if (hipError_t e = grid_check(blocks)) return e;
-    const RevealDecodeJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, correct ? 1u : 0u, max_errors, batches, dimension, mod, mont.pinv};
-    reveal_decode_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
-    return hipGetLastError();
-}
-
 size_t reveal_erasure_table_words(size_t n_rows) { return erase_table_words(n_rows); }
 
-hipError_t launch_reveal_erasure_finish(const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr, const uint64_t* d_xs,
-                                        const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks, uint32_t n_rows,
-                                        uint32_t max_errors, bool correct, size_t batches, size_t dimension, const ModParams& mod,
-                                        const MontParams& mont, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
-    if (checks == 0 || checks > (uint32_t)kMaxChecks || max_errors > checks / 2 || n_rows == 0 || n_rows > 65535)   // dec_pos is 16 bits wide
-        return hipErrorInvalidValue;
-    const uint64_t blocks = ceil_div(batches, kThreads);
+hipError_t launch_reveal_finish(RevealEnd end, const RevealFinishJob& job, const RevealFinishUnmask* unmask, int64_t* d_out,
+                                uint64_t* d_report, hipStream_t s) {
+    const uint32_t checks = job.checks, cap = job.max_errors;
+    // ---- what is refused, and what launches nothing ----
+    if (job.batches == 0 && end != RevealEnd::Erasures) return hipSuccess;
+    if (checks == 0 || checks > (uint32_t)kMaxChecks) return hipErrorInvalidValue;
+    if (job.n_rows == 0 || job.n_rows > 65535) return hipErrorInvalidValue;                   // dec_pos is 16 bits wide
+    if (end != RevealEnd::Locate && cap > checks / 2) return hipErrorInvalidValue;
+    if (end == RevealEnd::Decode && (checks < 2 || cap == 0)) return hipErrorInvalidValue;   // the caller states the cap
+    if (end == RevealEnd::Erasures && job.d_table == nullptr) return hipErrorInvalidValue;
+    const uint64_t blocks = ceil_div(job.batches, kThreads);
     if (hipError_t e = grid_check(blocks)) return e;
-    const uint64_t one = h_to_mont(1, mont.p);
-    reveal_erasure_setup_kernel<<<dim3(1), dim3(kThreads), 0, s>>>(d_ok, d_xs, n_rows, checks, mont.p, mont.pinv, one, d_table,
-                                                                   reinterpret_cast<unsigned long long*>(d_report));
-    if (hipError_t e = hipGetLastError()) return e;
-    if (batches == 0) return hipSuccess;
-    const RevealErasureJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, d_table, k, checks, n_rows, correct ? 1u : 0u,
-                             max_errors ? max_errors : (uint32_t)kDecodeErrors, batches, dimension, mod, mont.pinv};
-    reveal_erasure_finish_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, d_out, reinterpret_cast<unsigned long long*>(d_report));
-    return hipGetLastError();
-}
 
-hipError_t launch_reveal_unmask_finish(RevealUnmaskEnd end, const uint64_t* d_acc_lo, const int64_t* d_acc_hi, const uint64_t* d_corr,
-                                       const uint64_t* d_xs, const uint32_t* d_ok, uint64_t* d_table, uint32_t k, uint32_t checks,
-                                       uint32_t n_rows, uint32_t max_errors, bool correct, size_t batches, size_t dimension,
-                                       const ModParams& mod, const MontParams& mont, const uint64_t* d_mask_lo, const int64_t* d_mask_hi,
-                                       const ModParams& mask_mod, const uint32_t* d_gate_masks, const uint32_t* d_gate_results,
-                                       uint32_t results_pass_bits, int64_t* d_out, uint64_t* d_report, hipStream_t s) {
-    if (batches == 0) return hipSuccess;
-    if (checks == 0 || checks > (uint32_t)kMaxChecks || n_rows == 0 || n_rows > 65535) return hipErrorInvalidValue;   // dec_pos is 16 bits wide
-    if (end != RevealUnmaskEnd::Locate && max_errors > checks / 2) return hipErrorInvalidValue;
-    if (end == RevealUnmaskEnd::Decode && (checks < 2 || max_errors == 0)) return hipErrorInvalidValue;
-    if (end == RevealUnmaskEnd::Erasures && d_table == nullptr) return hipErrorInvalidValue;
-    const uint64_t blocks = ceil_div(batches, kThreads);
-    if (hipError_t e = grid_check(blocks)) return e;
-    const uint32_t fix = correct ? 1u : 0u;
-    const RevealUnmask U{d_mask_lo, d_mask_hi, d_mask_lo ? mask_mod : mod, d_gate_masks, d_gate_results, results_pass_bits};
     unsigned long long* report = reinterpret_cast<unsigned long long*>(d_report);
-    if (end == RevealUnmaskEnd::Locate) {
-        const RevealCheckJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, k, checks, n_rows, fix, batches, dimension, mod, mont.pinv};
-        reveal_check_unmask_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
-        return hipGetLastError();
+    if (end == RevealEnd::Erasures) {
+        reveal_erasure_setup_kernel<<<dim3(1), dim3(kThreads), 0, s>>>(job.d_ok, job.d_xs, job.n_rows, checks, job.mont.p, job.mont.pinv,
+                                                                       h_to_mont(1, job.mont.p), job.d_table, report);
+        if (hipError_t e = hipGetLastError()) return e;
+        if (job.batches == 0) return hipSuccess;           // the report's [6] and [7] are written all the same
     }
-    RevealErasureJob J{d_acc_lo, d_acc_hi, d_corr, d_xs, nullptr, k, checks, n_rows, fix, max_errors, batches, dimension, mod, mont.pinv};
-    if (end == RevealUnmaskEnd::Decode) {
-        reveal_decode_unmask_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
-        return hipGetLastError();
+    const RevealJob J{job.d_acc_lo, job.d_acc_hi, job.d_corr, job.d_xs, end == RevealEnd::Erasures ? job.d_table : nullptr, job.k, checks,
+                      job.n_rows, job.correct ? 1u : 0u, end == RevealEnd::Erasures && cap == 0 ? (uint32_t)kDecodeErrors : cap,
+                      job.batches, job.dimension, job.mod, job.mont.pinv};
+    const dim3 grid((unsigned)blocks), wg(kThreads);
+    if (unmask) {
+        const RevealUnmask U{unmask->d_mask_lo, unmask->d_mask_hi, unmask->d_mask_lo ? unmask->mask_mod : job.mod, unmask->d_gate_masks,
+                             unmask->d_gate_results, unmask->results_pass_bits};
+        if (end == RevealEnd::Locate) reveal_check_unmask_kernel<<<grid, wg, 0, s>>>(J, U, d_out, report);
+        else if (end == RevealEnd::Decode) reveal_decode_unmask_kernel<false><<<grid, wg, 0, s>>>(J, U, d_out, report);
+        else reveal_decode_unmask_kernel<true><<<grid, wg, 0, s>>>(J, U, d_out, report);
+    } else {
+        if (end == RevealEnd::Locate) reveal_check_finish_kernel<<<grid, wg, 0, s>>>(J, d_out, report);
+        else if (end == RevealEnd::Decode) reveal_decode_finish_kernel<<<grid, wg, 0, s>>>(J, d_out, report);
+        else reveal_erasure_finish_kernel<<<grid, wg, 0, s>>>(J, d_out, report);
     }
-    reveal_erasure_setup_kernel<<<dim3(1), dim3(kThreads), 0, s>>>(d_ok, d_xs, n_rows, checks, mont.p, mont.pinv, h_to_mont(1, mont.p), d_table,
-                                                                   report);
-    if (hipError_t e = hipGetLastError()) return e;
-    J.table = d_table;
-    if (max_errors == 0) J.cap = (uint32_t)kDecodeErrors;
-    reveal_decode_unmask_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(J, U, d_out, report);
     return hipGetLastError();
 }
 

@@ -43,6 +43,10 @@ K8_ALL = tuple(range(26))                                              # k8_62: 
 K8_TWELVE = (25, 0, 13, 7, 1, 19, 4, 22, 10, 16, 2, 11)                # k8_62: r = 2
 WIDE_300, WIDE_257 = tuple(range(300)), tuple(range(257))              # k3_wide: r = 296 and 253, positions past a byte
 PSS_260 = tuple((37 * i + 5) % 728 for i in range(260))                # pss155: r = 5, scattered (gcd(37, 728) = 1)
+# The finishes store a group of up to four secrets at a time, element j of it when j < have, the elements of the group below the
+# dimension.  k8_62 folds 4 + 4: dimension mod 8 = 1 .. 4 leaves the second group of the last batch with have = 0 and the first with
+# have = 1, 2, 3, 4; 6 and 7 leave the second with 2 and 3 (5 is d805's); one batch of dimension 1.  33 batches
+GUARD_DIMS = (257, 258, 259, 260, 262, 263, 1)
 
 
 def _cases():
@@ -105,6 +109,9 @@ def _cases():
     add("k3_wide-c16-d1-row", "k3_wide", 1, WIDE_300, 16, fault="row", expect="located", pin=(299,))
     # steered syndromes: the locate rule on geometric sequences whose ratio is a point, no point, and the node 1
     add("k3_62-c4-d769-steered", "k3_62", 769, ALL8, 4, fault="steered", pin=(7, 0, 3, 5))
+    # the guard of the store's partial group (GUARD_DIMS below): one faulty row at each
+    for dim in GUARD_DIMS:
+        add(f"k8_62-c8-d{dim}-row", "k8_62", dim, K8_ALL, 8, fault="row", expect="located")
     return out
 
 
@@ -112,6 +119,8 @@ CASES = _cases()
 BY_NAME = {c.name: c for c in CASES}
 SINGLE_FAULTS = ("row", "first", "last")      # exactly one faulty position: the correction is the other rows' reconstruction
 E2E = "k3_62-c4-d1000-row"
+GUARD = tuple(f"k8_62-c8-d{dim}-row" for dim in GUARD_DIMS)
+assert set(GUARD) <= set(BY_NAME)
 
 
 def batches(case):
@@ -203,6 +212,38 @@ def unchecked_python(case, rows, keep=None):
     R = rc.lagrange_matrix(p, k, w2, w3, tuple(case.indices[i] for i in keep))
     out = [sum(R[e][j] * (int(rows[i][b]) % p) for j, i in enumerate(keep)) % p for b in range(batches(case)) for e in range(k)]
     return np.array(out[:case.dim], dtype=np.int64)
+
+
+# ---- the store of a plain finish, shared by the three finish tables -------------------------------------------------------------
+SENTINEL = 0x5A5A5A5A5A5A5A5A                # what the GPU runners fill the output buffer with, dim + TAIL words
+TAIL = 8
+STORE_PLANTS = ("last_element_dropped", "second_group_unguarded")
+
+
+def last_batch_groups(case):
+    """(n, have) of every group of four of the LAST batch (every other batch has full groups): its secrets, and those of them below
+    the dimension"""
+    k = SCHEMES[case.scheme][1]
+    e = (batches(case) - 1) * k
+    return tuple((min(4, k - s0), max(0, min(min(4, k - s0), case.dim - (e + s0)))) for s0 in range(0, k, 4))
+
+
+def framed(model, case, rows, policy, plant=None):
+    """What a plain finish leaves in a SENTINEL-filled buffer of dim + TAIL words, by the table's `model` (its model_finish) - what the
+    GPU runners compare, tail included.  plant, a fault of STORE_PLANTS in the store: "last_element_dropped" (`have` one short in a
+    partial group: the last element stays), "second_group_unguarded" (the second group of the last batch of k = 8 is stored though it
+    is all padding: behind the output)"""
+    k = SCHEMES[case.scheme][1]
+    buf = [int(x) for x in model(case, rows, policy).out] + [SENTINEL] * TAIL
+    groups = last_batch_groups(case)
+    if plant == "last_element_dropped" and any(0 < have < n for n, have in groups):
+        buf[case.dim - 1] = SENTINEL
+    if plant == "second_group_unguarded" and k == 8 and groups[1][1] == 0:
+        padded = model(case._replace(dim=batches(case) * k), rows, policy).out
+        e0 = (batches(case) - 1) * k + 4
+        for j in range(4):
+            buf[e0 + j] = int(padded[e0 + j])
+    return buf
 
 
 # ---- rows -----------------------------------------------------------------------------------------------------------------------

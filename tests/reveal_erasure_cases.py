@@ -130,13 +130,18 @@ def _cases():
     add("k3_62", "k3_62", 769, ALL8, 4, (2,), "steered", pin=(0, 3, 7))
     add("k8_62", "k8_62", 805, K8_ALL, 16, (4, 8, 20), "steered", pin=tuple(range(1, 26, 2)))
     add("k3_wide", "k3_wide", 769, WIDE_300, 16, (64, 256), "steered", pin=(0, 63, 65, 127, 128, 191, 192, 255, 257, 270, 280, 290, 298, 299))
-    return out, parent
+    wide = len(out)
+    # the guard of the store's partial group (reveal_check_cases.GUARD_DIMS): one refused and one faulty row at each
+    for dim in vc.GUARD_DIMS:
+        add("k8_62", "k8_62", dim, K8_ALL, 16, (12,), 1)
+    return out, parent, wide
 
 
-CASES, PARENT_CASES = _cases()
+CASES, PARENT_CASES, WIDE_CASES = _cases()
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
-NEW = tuple(c.name for c in CASES[PARENT_CASES:])                            # ... and these came with it
+NEW = tuple(c.name for c in CASES[PARENT_CASES:WIDE_CASES])                  # ... and these came with it
+GUARD = tuple(c.name for c in CASES[WIDE_CASES:])                            # ... and these with the store the finishes share
 E2E = "k3_62-c4-d764-f2-e1-zero"
 
 

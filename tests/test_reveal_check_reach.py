@@ -185,3 +185,22 @@ def test_a_planted_model_fault_is_noticed(plant):
             noticed.append(name)
     print(plant, "noticed by", noticed)
     assert noticed, plant
+
+
+# ---- the store the plain finishes share: what the guard cases are there for ---------------------------------------------------------
+@pytest.mark.parametrize("plant", vc.STORE_PLANTS)
+def test_the_guard_cases_notice_a_planted_store_fault(plant):
+    """the GPU runners check the output against the model and the words behind it against the sentinel - together the buffer of
+    vc.framed(): a store that drops the last element of a partial
+    group, or stores an all-padding second group, leaves other words there at every dimension the guard cases were chosen for"""
+    assert [vc.BY_NAME[n].dim for n in vc.GUARD] == list(vc.GUARD_DIMS) and all(vc.BY_NAME[n].scheme == "k8_62" for n in vc.GUARD)
+    hit = []
+    for name in vc.GUARD:
+        case, rows = vc.BY_NAME[name], vc.build(name).rows
+        fin = vc.model_finish(case, rows, vc.CORRECT)
+        assert fin.report[1] == fin.report[2] == vc.batches(case), "every batch of a guard case is corrected"
+        clean = vc.framed(vc.model_finish, case, rows, vc.CORRECT)
+        assert clean[case.dim:] == [vc.SENTINEL] * vc.TAIL and vc.SENTINEL not in clean[:case.dim]
+        if vc.framed(vc.model_finish, case, rows, vc.CORRECT, plant) != clean:
+            hit.append(case.dim % 8)
+    assert sorted(hit) == ([1, 1, 2, 3, 6, 7] if plant == "last_element_dropped" else [1, 1, 2, 3, 4])
